@@ -2,7 +2,24 @@
 """Throughput benchmark of the cardiac cine-MRI SR train step on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--models edsr,duf] [--config cfg2|cfg3|cfg4|cfg5]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (driver, N > 1)
+
+A plain run does what the headline figure needs and no more: it sets up the
+config's first model (cfg2: EDSR), warms up, times --steps train steps and
+prints the JSON line (value, ms_per_step and the roofline of the launches
+timed inside those steps).  --full adds everything else the benchmark
+measures: the config's other models (cfg2: DUF, the north-star line), the
+per-step metric timing, the measured MFMA / HBM peaks, the CPU baseline and
+(N > 1) the communication timing.  Models named with --models / --model are
+run as named, with or without --full.
+--dump-outputs DIR writes what the last timed step computed, per model, as
+float32 DIR/<model>_<name>.npy: loss, out (the generator's output; out_00..
+for DRF's frame list), grads and params (every parameter's gradient / value
+after the step's Adam update, flattened in parameter order).  An array over
+its share of the 60 MiB budget is stored as a fixed, seeded sample of its
+elements.  Weights and data are seeded, so two runs with the same arguments
+see identical inputs.
 
 With --gpus N > 1 and no torchrun environment, bench.py starts the N ranks
 itself (one process per GPU, before any GPU call); under torchrun --gpus must
@@ -14,7 +31,8 @@ over one synthetic batch of the BASELINE cfg-2 shape: per GPU a 4 x 16 x
 scaling: data-parallel, gradients all-reduced over RCCL, BatchNorm statistics
 synchronised for DUF).
 
-Models (each timed on its own, all reported in the one JSON line):
+Models (each timed on its own, all reported in the one JSON line; a plain run
+without --models times only the config's first):
   edsr  EDSRNet on the volume's 64 slices (2-D residual blocks + PixelShuffle)
   duf   DUFNet on the volume's 64 seven-frame cyclic windows (Conv3d 3x3x3 /
         BatchNorm3d dense blocks + dynamic upsampling filter)
@@ -33,14 +51,14 @@ roofline: the model's dominant conv, forward + data gradient + weight
 stacks), cfg4 (ACDC full volumes: DUF on 2 uncropped 30-frame cine
 volumes of 64 x 64 LR / 256 x 256 HR per GPU), cfg5 (ACDC + DSB15 mixed,
 fp16, batch 8 per GPU, EDSR + DUF).
-comm (N > 1): the data-parallel traffic of one step -- gradient bytes and
+comm (--full, N > 1): the data-parallel traffic of one step -- gradient bytes and
           buckets, and the time of the step's bucket all-reduces and SyncBN
           all-reduces each run alone after the timed region (HIP events), to
           set beside ms_per_step: what the overlap with backward must hide.
-measured_peak: this device's dense bf16 MFMA rate and HBM copy rate from
+measured_peak (--full): this device's dense bf16 MFMA rate and HBM copy rate from
           two microbenchmarks (vsrk_peak_mfma / vsrk_peak_copy), with each
           roofline's fraction of the measured MFMA rate beside the vendor one.
-cpu_baseline: the CPU fp32 restatement of the same generator (oracle/,
+cpu_baseline (--full): the CPU fp32 restatement of the same generator (oracle/,
           the reference's algorithm) timed on this host for a bounded sample
           (rank 0, N = 1 only), threads = the CPU share of this process.
 """
@@ -54,6 +72,7 @@ import sys
 import time
 from pathlib import Path
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -306,7 +325,39 @@ def write_units(path, model, precision, rows):
                     f"{r['frac']:>6.3f} {r['hbm_frac'] * HBM_PEAK / 1e12:>6.2f} {r['bound_frac']:>6.3f}\n")
 
 
-def run_model(name, args, world, rank, dev):
+DUMP_BYTES = 60 * 2 ** 20  # --dump-outputs: the 60 MiB budget all files of a run share
+
+
+def _dump_array(path, t, limit):
+    """Save tensor t flattened as float32 .npy: whole when it has at most
+    ``limit`` elements, else the elements at a fixed, seeded set of ``limit``
+    distinct indices (ascending)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > limit:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randperm(flat.numel(), generator=g)[:limit].sort().values
+        flat = flat[idx.to(flat.device)]
+    np.save(path, flat.float().cpu().numpy())
+
+
+def dump_outputs(dirname, name, n_models, loss, out, net):
+    """What the last timed step handed back: its loss and generator output,
+    and the gradients and updated weights it left on the net."""
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    budget = DUMP_BYTES // 4 // n_models  # float32 elements of this model
+    _dump_array(d / f"{name}_loss.npy", loss, budget)
+    if isinstance(out, list):
+        for i, o in enumerate(out):
+            _dump_array(d / f"{name}_out_{i:02d}.npy", o, budget // 2 // len(out))
+    else:
+        _dump_array(d / f"{name}_out.npy", out, budget // 2)
+    params = [p for p in net.parameters() if p.grad is not None]
+    _dump_array(d / f"{name}_grads.npy", torch.cat([p.grad.reshape(-1).float() for p in params]), budget // 4 - 1)
+    _dump_array(d / f"{name}_params.npy", torch.cat([p.reshape(-1).float() for p in params]), budget // 4 - 1)
+
+
+def run_model(name, args, world, rank, dev, n_models=1):
     spec = MODELS[name]
     torch.manual_seed(0)  # identical initial weights on every rank
     net = getattr(nets, spec["cls"])(**spec["kwargs"]).to(dev).set_precision(args.precision).train()
@@ -328,13 +379,17 @@ def run_model(name, args, world, rank, dev):
         if F.timer is not None:
             F.timer.phase = p
 
-    def step():
+    kept = []  # the generator output of the last timed step (--dump-outputs)
+
+    def step(keep=False):
         phase("fwd")
         out = net(x)
         if isinstance(out, list):
             loss = torch.stack([l1(o, t) for o, t in zip(out, y)]).mean()
         else:
             loss = l1(out, y)
+        if keep:
+            kept.append(out)
         opt.zero_grad(set_to_none=True)
         phase("bwd")
         loss.backward()
@@ -352,8 +407,8 @@ def run_model(name, args, world, rank, dev):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss = step(keep=bool(args.dump_outputs) and i == args.steps - 1)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -378,8 +433,10 @@ def run_model(name, args, world, rank, dev):
         t = torch.tensor([elapsed], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
-    comm = comm_report(net, sync, dev) if world > 1 else None
-    metrics = metric_report(net, x, y, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, name, n_models, loss, kept.pop(), net)
+    comm = comm_report(net, sync, dev) if world > 1 and args.full else None
+    metrics = metric_report(net, x, y, dev) if args.full else None
     vox_step = B * T * H * W
     peak = PEAK[args.precision]
     achieved = flop / kernel_s if kernel_s > 0 else None
@@ -419,7 +476,8 @@ def run_model(name, args, world, rank, dev):
         ks = net._seq_run_k
         res["wgrad_runs"] = {"chunk_frames": net._seq_run_frames,
                              "run_frames": {str(k): sorted(n for n, v in ks.items() if v == k) for k in sorted(set(ks.values()))}}
-    res["metrics"] = metrics
+    if metrics is not None:
+        res["metrics"] = metrics
     del net, opt, sync
     torch.cuda.empty_cache()
     return res
@@ -442,7 +500,7 @@ def worker(args, world, rank, local):
     _native.load()
 
     names = [m for m in args.models.split(",") if m]
-    results = {m: run_model(m, args, world, rank, dev) for m in names}
+    results = {m: run_model(m, args, world, rank, dev, len(names)) for m in names}
     if rank == 0:
         first = results[names[0]]
         out = {
@@ -452,7 +510,7 @@ def worker(args, world, rank, local):
             "config": first["config"], "roofline": first["roofline"], "final_loss": first["final_loss"],
             "models": results,
         }
-        if not args.no_peaks:
+        if args.full and not args.no_peaks:
             # the measured ceilings beside the vendor peak the fractions use
             pk = F.measured_peaks(dev)
             out["measured_peak"] = pk
@@ -470,7 +528,7 @@ def worker(args, world, rank, local):
                                  "frac_of_measured_peak": rf.get("frac_of_measured_peak"),
                                  "launches_per_step": rf["launches_per_step"],
                                  "tflop_per_step": rf["flop_per_step"] / 1e12, "by_direction": rf["by_direction"]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             for m in names:
                 results[m]["cpu_baseline"] = cpu_baseline(m)
             out["cpu_baseline"] = results[names[0]]["cpu_baseline"]
@@ -501,7 +559,7 @@ def _free_port() -> int:
         return s.getsockname()[1]
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -512,17 +570,29 @@ def main():
                     help="comma-separated subset of " + ",".join(MODELS))
     ap.add_argument("--model", default=None, help="a single model (same as --models NAME)")
     ap.add_argument("--precision", default=None, choices=["bf16", "fp16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-peaks", action="store_true", help="skip the measured MFMA / HBM peak microbenchmarks")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the config's other models, the metric timing, the measured peaks, the CPU "
+                         "baseline and (N > 1) the communication timing")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's loss, output, gradients and weights to DIR/<model>_<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-peaks", action="store_true",
+                    help="with --full: skip the measured MFMA / HBM peak microbenchmarks")
     ap.add_argument("--units", default=None, help="append the roofline kernel's per-launch table (one step) to FILE")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     cfg = CONFIGS[args.config]
-    args.models = args.model or args.models or cfg["models"]
+    # a plain run times the headline model alone; --full (or naming them) runs all
+    args.models = args.model or args.models or (cfg["models"] if args.full else cfg["models"].split(",")[0])
     args.precision = args.precision or cfg["precision"]
-    apply_config(args)
     for m in args.models.split(","):
         if m not in MODELS:
             ap.error(f"unknown model {m!r}")
+    return args
+
+
+def main():
+    args = parse_args()
+    apply_config(args)
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is not None:

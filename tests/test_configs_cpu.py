@@ -3,10 +3,9 @@ unchanged"; SURVEY §2 row 19, §5 Config/flags).
 
 Every object of a config is ``{name, kwargs}`` resolved by name
 (src/main.py:167-178).  These tests load the build's own configs for the
-BASELINE configurations and the reference's own training configs
-(configs/train/acdc_{sisr,misr,vsr}_config.yaml, with their placeholders --
-MyNet, MyLoss, ``value`` -- filled in) and build every object through
-vsr_amd.config, as main.py:16-108 does: datasets over a small NIfTI tree in
+BASELINE configurations (configs/train/*.yaml, configs/test/*.yaml: the
+reference's schema with its placeholders filled in) and build every object
+through vsr_amd.config, as main.py:16-108 does: datasets over a small NIfTI tree in
 the reference's on-disk layout, dataloaders, net, losses, metrics,
 optimizer, scheduler, logger, monitor and trainer.  Construction only (CPU);
 tests/test_configs_gpu.py runs an epoch.
@@ -21,7 +20,6 @@ from nifti_tree import make_tree
 from vsr_amd import config as C
 
 ROOT = Path(__file__).resolve().parent.parent
-REF = Path("/root/reference/configs")
 OWN = sorted((ROOT / "configs" / "train").glob("*.yaml"))
 
 
@@ -89,71 +87,28 @@ def test_own_configs_build(path, tree, tmp_path):
     assert [type(f).__name__ for f in trainer.metric_fns] == [c["name"] for c in cfg["metrics"]]
 
 
-# The reference's own configs with the placeholders filled in the way the
-# BASELINE configurations use them (SURVEY §8 canonical constructors).
-FILL = {
-    "acdc_sisr_config.yaml": ("EDSRNet", dict(in_channels=1, out_channels=1, num_resblocks=2, num_features=16,
-                                              upscale_factor=4, res_scale=0.1), {}),
-    "acdc_misr_config.yaml": ("DUFNet", dict(in_channels=1, out_channels=1, num_frames=7, size_filter=5,
-                                             upscale_factor=4, backbone="_DenseLayer16"), {"num_frames": 7}),
-    "acdc_vsr_config.yaml": ("DRFNet", dict(in_channels=1, out_channels=1, num_features=16, num_groups=2,
-                                            upscale_factor=4), {"num_frames": 3}),
-}
+OWN_TEST = sorted((ROOT / "configs" / "test").glob("*.yaml"))
 
 
-@pytest.mark.skipif(not REF.is_dir(), reason="the reference tree is not on this machine")
-@pytest.mark.parametrize("name", sorted(FILL))
-def test_reference_train_configs_build(name, tree, tmp_path):
-    """configs/train/acdc_*_config.yaml of the reference, read unchanged except
-    for its placeholders, resolve every name through vsr_amd."""
-    text = (REF / "train" / name).read_text()
-    cfg = yaml.safe_load(text)
-    net_name, net_kwargs, ds_extra = FILL[name]
-    cfg["net"] = {"name": net_name, "kwargs": net_kwargs}
-    cfg["losses"] = [{"name": "L1Loss", "weight": 1.0}]
-    cfg["main"]["saved_dir"] = str(tmp_path / "out")
-    kw = cfg["dataset"]["kwargs"]
-    kw["downscale_factor"] = 4
-    kw.update(ds_extra)
-    for a in kw.get("augments") or []:
-        if a["name"] == "RandomCropPatch":
-            a["kwargs"].update(size=[8, 8], ratio=4)
-    cfg["dataloader"]["kwargs"].update(train_batch_size=2, num_workers=0)
-    cfg["optimizer"]["kwargs"]["lr"] = 1e-4
-    cfg["trainer"]["kwargs"]["num_epochs"] = 1
-    _point_data(cfg, tree)
-    # nothing else in the file is a placeholder
-    flat = yaml.safe_dump(cfg)
-    assert "value" not in flat.split() and "MyNet" not in flat and "MyLoss" not in flat
-    trainer = C.build_train(C.Box(cfg), device="cpu")
-    assert type(trainer).__name__ == cfg["trainer"]["name"]
-    assert type(trainer.logger).__name__ == cfg["logger"]["name"]
-    assert type(trainer.monitor).__name__ == "Monitor"
-    assert [type(m).__name__ for m in trainer.metric_fns] == ["PSNR", "SSIM"]
-    batch = next(iter(trainer.train_dataloader))
-    inputs, targets = trainer._get_inputs_targets(batch)
-    if isinstance(inputs, list):
-        assert len(inputs) == ds_extra["num_frames"]
-
-
-@pytest.mark.skipif(not REF.is_dir(), reason="the reference tree is not on this machine")
-@pytest.mark.parametrize("name", ["acdc_sisr_config.yaml", "acdc_misr_config.yaml", "acdc_vsr_config.yaml"])
-def test_reference_test_configs_build(name, tree, tmp_path):
-    cfg = yaml.safe_load((REF / "test" / name).read_text())
-    net_name, net_kwargs, ds_extra = FILL[name]
-    cfg["net"] = {"name": net_name, "kwargs": net_kwargs}
-    cfg["losses"] = [{"name": "L1Loss", "weight": 1.0}]
-    cfg["metrics"] = [m for m in cfg["metrics"] if m["name"] != "MyMetric"]
+@pytest.mark.parametrize("path", OWN_TEST, ids=[p.stem for p in OWN_TEST])
+def test_own_test_configs_build(path, tree, tmp_path):
+    """configs/test/*.yaml (the reference's test-config schema, placeholders
+    filled) resolve every name through vsr_amd.config.build_test, as
+    main.py does for a prediction run."""
+    cfg = yaml.safe_load(path.read_text())
+    assert {"main", "dataset", "dataloader", "net", "losses", "metrics", "predictor"} <= set(cfg)
     cfg["main"]["saved_dir"] = str(tmp_path / "pred")
     cfg["main"].pop("loaded_path", None)
     cfg["predictor"]["kwargs"].update(saved_dir=str(tmp_path / "pred"), device="cpu")
-    kw = cfg["dataset"]["kwargs"]
-    kw["downscale_factor"] = 4
-    kw.update(ds_extra)
     cfg["dataloader"]["kwargs"]["num_workers"] = 0
     _point_data(cfg, tree)
     pred = C.build_test(C.Box(cfg), device="cpu")
+    from vsr_amd import nets
     assert type(pred).__name__ == cfg["predictor"]["name"]
+    assert isinstance(pred.net, getattr(nets, cfg["net"]["name"]))
+    assert [type(f).__name__ for f in pred.loss_fns] == [c["name"] for c in cfg["losses"]]
+    assert [type(f).__name__ for f in pred.metric_fns] == [c["name"] for c in cfg["metrics"]]
+    assert len(pred.test_dataloader.dataset) > 0
 
 
 def test_loss_resolution_order():

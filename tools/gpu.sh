@@ -7,8 +7,8 @@
 #   tests                 the whole -m gpu suite
 #   tests:FILES           named test files / node ids (comma separated)
 #   smoke                 __graft_entry__.smoke()
-#   bench[:CFG[:MODELS]]  bench.py line (CFG default cfg2; MODELS default the config's)
-#   quick[:CFG[:MODELS]]  bench.py, 5 steps, no CPU baseline / peaks
+#   bench[:CFG[:MODELS]]  bench.py --full line (CFG default cfg2; MODELS default the config's, all of them)
+#   quick[:CFG[:MODELS]]  bench.py --full, 5 steps, no CPU baseline / peaks (every model, metric timing kept)
 #   prof:CFG:MODELS       rocprofv3 --kernel-trace --stats of a short bench run + top kernels
 #   traffic:MODELS        separate FETCH_SIZE and WRITE_SIZE --pmc passes over a 1-step bench
 #   pmc:CASE:WHAT[:PATHS] instruction / wait / LDS / HBM counter passes over tools/conv_microbench.py
@@ -49,6 +49,7 @@ for STEP in "$@"; do
     bench|quick)
       CFG=${A1:-cfg2}; EXTRA=""
       [ -n "$A2" ] && EXTRA="--models $A2"
+      EXTRA="$EXTRA --full"  # every model of the config, metric timing, peaks, CPU baseline
       [ $KIND = quick ] && EXTRA="$EXTRA --steps 5 --warmup 2 --no-cpu-baseline --no-peaks"
       F=$O.$KIND.$CFG${A2:+.${A2//,/_}}
       timeout -k 10 900 python bench.py --config $CFG $EXTRA --units $F.units.txt > $F.json 2> $F.err || { tail -20 $F.err; exit 1; }
