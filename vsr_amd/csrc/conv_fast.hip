@@ -55,7 +55,8 @@ extern "C" int vsrk_conv_set_path(const char* path, int32_t mode) {
   else if (p == "roll_fold") vsrk_conv_set_roll_fold_mode(mode);
   else if (p == "stencil") vsrk_conv_set_stencil_mode(mode);
   else if (p == "pw_wide") g_pw_wide_mode = mode;
-  else VSRK_CHECK(false, "conv_set_path: unknown path '%s' (fast, pw, roll, roll_wr, roll_fold, thin, wgrad_pipe, wgrad_roll, wgrad_row, stencil)",
+  else if (p == "row") vsrk_conv_set_row_mode(mode);
+  else VSRK_CHECK(false, "conv_set_path: unknown path '%s' (fast, pw, pw_wide, roll, roll_wr, roll_fold, row, thin, wgrad_pipe, wgrad_roll, wgrad_row, stencil)",
                   path);
   return VSRK_OK;
 }

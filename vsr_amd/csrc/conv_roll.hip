@@ -1519,6 +1519,16 @@ static int roll_fwd_one(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vo
                          t->c;
     if (span >= (1ll << 31) || t->sn < 0 || t->sd < 0 || t->sh < 0 || t->sw < 0) return 0;
   }
+  if (g_roll_wr_mode < 0) {
+    const char* e = getenv("VSRK_ROLL_WRES");
+    g_roll_wr_mode = (e && e[0] == '0') ? 0 : 1;
+  }
+  // EDSR's 64 -> 64 body convs: the row-walking kernel (conv_row.hip) takes
+  // the forms it covers.  An explicit roll_wr setting (0 or 2) asks for one
+  // of the tile kernel's two forms: the row kernel stands aside.
+  if (!k3 && sp == SP_NONE && !pmask && !bnred && g_roll_wr_mode == 1) {
+    if (const int rw = vsrk_conv_fwd_row(d, x, w_packed, bias, residual, mask, y, s)) return rw;
+  }
   // a shuffled view walks the low-res grid: its row / column strides are r
   // physical rows / columns (the phase lives in the channel offset table)
   auto rview = [](const vsrk_tensor5* t) {
@@ -1599,10 +1609,6 @@ static int roll_fwd_one(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vo
   // -- EDSR's 64 -> 64 body convs -- or (3-D) whole-depth tiles, where a
   // reload per tile is amortised over nsl x nchunk stages (DUF's data
   // gradients 32 -> F).  VSRK_ROLL_WRES=0 turns it off (A/B).
-  if (g_roll_wr_mode < 0) {
-    const char* e = getenv("VSRK_ROLL_WRES");
-    g_roll_wr_mode = (e && e[0] == '0') ? 0 : 1;
-  }
   const int wres_mode = g_roll_wr_mode;
   const size_t nb = k3 ? RollGeo<3, 1>::NB : RollGeo<1, 2>::NB;
   const size_t wbytes = (size_t)a.nchunk * nb * 1024;

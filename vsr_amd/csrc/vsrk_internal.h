@@ -70,6 +70,15 @@ void vsrk_conv_set_roll_fold_mode(int mode);
 int vsrk_conv_fwd_roll_fold(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed, const float* bias,
                             const float* pro_scale, const float* pro_shift, const vsrk_tensor5* y, hipStream_t s);
 
+// row-walking 16-bit Conv 3x3 64 -> 64 (conv_row.hip): forward / data gradient
+// of EDSR's body convs, reached from conv_roll.hip's 2-D branch after its
+// checks; 1 launched, 0 not eligible, < 0 -(error status).
+// vsrk_conv_set_row_mode: -1 default (VSRK_CONV_ROW, read at load time; unset:
+// the forms that measured faster than the tile kernel), 0 off, 1 every form
+int vsrk_conv_fwd_row(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed, const float* bias,
+                      const vsrk_tensor5* residual, const vsrk_tensor5* mask, const vsrk_tensor5* y, hipStream_t s);
+void vsrk_conv_set_row_mode(int mode);
+
 // pointwise (1x1x1) bf16 conv (conv_pw.hip): forward / data gradient and
 // weight gradient; same return convention (the wgrad launches its own reduce)
 int vsrk_conv_fwd_pw(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed, const float* bias,

@@ -409,13 +409,17 @@ def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, k, pad, dw: torch.Tensor, dbia
 
 def set_conv_path(path: str, mode: int) -> None:
     """Select a conv kernel family ("fast", "pw", "pw_wide", "roll", "roll_wr", "roll_fold", "thin", "wgrad_pipe",
-    "wgrad_roll", "wgrad_row"):
+    "wgrad_roll", "wgrad_row", "row", "stencil"):
     -1 default, 0 off, 1 on
     (for "roll" / "wgrad_roll": 1 forces the rolling kernel on every eligible
     shape, the default also skips shallow output depths where it is slower;
     "wgrad_row": 2 also takes the sub-pixel tap-skip views; "roll_wr": the
     rolling conv's resident weights, 2 also with the prefetched residual / mask
-    epilogue, where they are slower)."""
+    epilogue, where they are slower, and 0 or 2 keep the row kernel aside;
+    "row": the row-walking 3x3 64 -> 64 conv of EDSR's body, reached through
+    "roll"; its default, read from VSRK_CONV_ROW when the library loads,
+    routes the epilogue forms that measured faster than the tile kernel, 1
+    routes every form it covers)."""
     N.check(_lib().vsrk_conv_set_path(path.encode(), int(mode)), "conv_set_path")
 
 
