@@ -435,6 +435,22 @@ int vsrk_duf_dynfilter_bwd(const float* x, const float* logits, const float* gra
                            int32_t w, int32_t size_filter, int32_t upscale, void* grad_logits, void* grad_residual,
                            int32_t grad_dtype, void* stream);
 
+/* Interpolating upsampling by an integer factor r >= 1 and its adjoint:
+ * F.interpolate(x, scale_factor=r, mode, align_corners) -- SRFBN's global skip
+ * (srfb_net.py:47: bilinear, align_corners=False) and the Bicubic baseline
+ * (bicubic.py:15: bicubic, align_corners=True).  Contiguous planes: x is
+ * (planes, h, w), y is (planes, r*h, r*w), both of `dtype` (VSRK_F32, VSRK_BF16
+ * or VSRK_F16); arithmetic is fp32.  mode: 0 bilinear, 1 bicubic (A = -0.75);
+ * source coordinates are torch's ((dst + 0.5) / r - 0.5, or
+ * dst * (h - 1) / (r*h - 1) with align_corners), tap indices clamped to the
+ * image.  accumulate = 1: y += Up(x) / gx += Up^T(gy).  The adjoint is a gather
+ * in a fixed order (no atomics: bitwise reproducible).  An output of 2^32
+ * elements or more is VSRK_ERR_INVALID. */
+int vsrk_upsample2d_fwd(int32_t dtype, const void* x, int64_t planes, int32_t h, int32_t w, int32_t r, int32_t mode,
+                        int32_t align_corners, int32_t accumulate, void* y, void* stream);
+int vsrk_upsample2d_bwd(int32_t dtype, const void* gy, int64_t planes, int32_t h, int32_t w, int32_t r, int32_t mode,
+                        int32_t align_corners, int32_t accumulate, void* gx, void* stream);
+
 const char* vsrk_last_error(void);
 const char* vsrk_version(void);
 

@@ -134,6 +134,8 @@ _SIGS = {
     "vsrk_ssim3d_workspace_size": (C.c_size_t, [C.c_int32] * 5),
     "vsrk_resize_bicubic": (C.c_int, [_P] + [C.c_int32] * 5 + [_P, C.c_int32, _P]),
     "vsrk_ssim3d": (C.c_int, [_P, _P] + [C.c_int32] * 6 + [C.c_float] * 3 + [_P, _P, _P, C.c_size_t, _P]),
+    "vsrk_upsample2d_fwd": (C.c_int, [C.c_int32, _P, C.c_int64] + [C.c_int32] * 6 + [_P, _P]),
+    "vsrk_upsample2d_bwd": (C.c_int, [C.c_int32, _P, C.c_int64] + [C.c_int32] * 6 + [_P, _P]),
     "vsrk_last_error": (C.c_char_p, []),
     "vsrk_version": (C.c_char_p, []),
 }

@@ -480,6 +480,48 @@ def add(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     return out
 
 
+UPSAMPLE_MODES = {"bilinear": 0, "bicubic": 1}
+
+
+def _upsample(fn, what: str, small: torch.Tensor, big: torch.Tensor, src: torch.Tensor, dst: torch.Tensor, mode,
+              align_corners: bool, r: int, accumulate: bool) -> torch.Tensor:
+    """The shared argument checks of upsample2d / upsample2d_bwd: `small` is
+    the (..., h, w) side, `big` the (..., r*h, r*w) side."""
+    m = UPSAMPLE_MODES[mode] if isinstance(mode, str) else int(mode)
+    r = int(r)
+    if small.dim() < 2 or big.dim() != small.dim():
+        raise ValueError(f"{what}: expected (..., h, w) and (..., r*h, r*w), got {tuple(small.shape)} and "
+                         f"{tuple(big.shape)}")
+    h, w = small.shape[-2:]
+    if tuple(big.shape) != (*small.shape[:-2], h * r, w * r):
+        raise ValueError(f"{what}: {tuple(small.shape)} x{r} does not give {tuple(big.shape)}")
+    if small.dtype != big.dtype:
+        raise TypeError(f"{what}: dtype mismatch ({small.dtype} and {big.dtype})")
+    if not (small.is_contiguous() and big.is_contiguous()):
+        raise ValueError(f"{what}: tensors must be contiguous planes")
+    if not (small.is_cuda and big.is_cuda):
+        raise RuntimeError("vsrk ops need device tensors (no CPU fallback)")
+    planes = small.numel() // max(h * w, 1)
+    N.check(fn(N.dtype_code(small.dtype), src.data_ptr(), planes, h, w, r, m, 1 if align_corners else 0,
+               1 if accumulate else 0, dst.data_ptr(), N.stream_ptr(small.device)), what)
+    return dst
+
+
+def upsample2d(x: torch.Tensor, y: torch.Tensor, mode, align_corners: bool, r: int,
+               accumulate: bool = False) -> torch.Tensor:
+    """y [+]= F.interpolate(x, scale_factor=r, mode=mode, align_corners=align_corners)
+    for contiguous x (..., h, w) and y (..., r*h, r*w) of one dtype (fp32 /
+    bf16 / fp16; fp32 arithmetic).  mode: 'bilinear' | 'bicubic' (or 0 | 1)."""
+    return _upsample(_lib().vsrk_upsample2d_fwd, "upsample2d_fwd", x, y, x, y, mode, align_corners, r, accumulate)
+
+
+def upsample2d_bwd(gy: torch.Tensor, gx: torch.Tensor, mode, align_corners: bool, r: int,
+                   accumulate: bool = False) -> torch.Tensor:
+    """gx [+]= the adjoint of upsample2d applied to gy (..., r*h, r*w) -> gx
+    (..., h, w): a fixed-order gather, bitwise reproducible."""
+    return _upsample(_lib().vsrk_upsample2d_bwd, "upsample2d_bwd", gx, gy, gy, gx, mode, align_corners, r, accumulate)
+
+
 def loss_fwd(kind: int, param: float, out: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     """Mean-reduced loss of two fp32 tensors -> device scalar."""
     lib = _lib()

@@ -12,8 +12,11 @@ its convolutions / batch norms on MI355X:
       projections, drf_net.py:93,100)                                   -> HipConv2d (sub-pixel form)
   nn.ConvTranspose2d(k, s, p) (DRF's up projections, drf_net.py:81,86)  -> HipConvTranspose2d
   nn.BatchNorm3d (duf_net.py:116,198,201)                               -> HipBatchNorm3d
+  nn.Upsample(scale_factor=r, mode='bilinear' | 'bicubic'), integer r (or a
+      pair of equal integers), 4-D input (bicubic.py:15)                -> HipUpsample
 
-Activations, PixelShuffle and tensor plumbing stay torch ops.  The fused
+Other nn.Upsample forms (nearest, trilinear, size=, a non-integer scale) are
+left as they are.  Activations, PixelShuffle and tensor plumbing stay torch ops.  The fused
 generators in vsr_amd.nets are the fast path; these modules trade a layout
 conversion per op for drop-in generality.
 """
@@ -79,6 +82,30 @@ class HipBatchNorm3d(nn.BatchNorm3d):
         return torch.ops.vsrk.batch_norm(x, self.weight, self.bias, st, use_batch, False)
 
 
+def _int_scale(sf) -> int | None:
+    """The integer factor of an nn.Upsample scale_factor (a number or a pair of
+    equal numbers), or None."""
+    if isinstance(sf, (tuple, list)):
+        if len(sf) != 2 or sf[0] != sf[1]:
+            return None
+        sf = sf[0]
+    if sf is None or float(sf) != int(sf) or int(sf) < 1:
+        return None
+    return int(sf)
+
+
+class HipUpsample(nn.Upsample):
+    """nn.Upsample(scale_factor=r, mode='bilinear' | 'bicubic') on
+    vsrk::upsample2d for 4-D inputs; anything else runs nn.Upsample's own forward."""
+
+    def forward(self, input):
+        r = _int_scale(self.scale_factor)
+        if (input.dim() != 4 or r is None or self.size is not None or self.mode not in ("bilinear", "bicubic")
+                or getattr(self, "recompute_scale_factor", None)):
+            return super().forward(input)
+        return torch.ops.vsrk.upsample2d(input, r, self.mode, bool(self.align_corners))
+
+
 def _convert(m: nn.Module) -> nn.Module | None:
     if type(m) is nn.Conv2d:
         if _supported_conv(m):
@@ -96,6 +123,9 @@ def _convert(m: nn.Module) -> nn.Module | None:
         new = HipConvTranspose2d.__new__(HipConvTranspose2d)
     elif type(m) is nn.BatchNorm3d:
         new = HipBatchNorm3d.__new__(HipBatchNorm3d)
+    elif (type(m) is nn.Upsample and m.mode in ("bilinear", "bicubic") and m.size is None
+          and _int_scale(m.scale_factor) is not None):
+        new = HipUpsample.__new__(HipUpsample)
     else:
         return None
     new.__dict__ = m.__dict__  # same parameters, buffers and hyper-parameters

@@ -48,6 +48,7 @@ from __future__ import annotations
 
 import math
 import os
+import types
 
 import torch
 import torch.nn as nn
@@ -172,9 +173,23 @@ class _DRFBase(BaseNet):
         if upscale_factor not in [2, 3, 4, 8]:
             raise ValueError(f"The upscale factor should be 2, 3, 4 or 8. Got {upscale_factor}.")
         self.upscale_factor = upscale_factor
-        self.in_block = _InBlock(in_channels, num_features)
-        self.f_block = _FBlock(num_features, num_groups, upscale_factor)
-        self.out_block = _OutBlock(num_features, out_channels, upscale_factor)
+        self._build_blocks()
+
+    # -- the pieces a sibling network on the same feedback machinery overrides
+    # (SRFBNet, srfb_net.py): the block attributes, the skip into the
+    # reconstruction and the reconstruction itself, forward and backward
+    _FEATURE_SKIP = True  # reconstruction input = in_features + f_features (drf_net.py:46)
+
+    def _build_blocks(self):
+        """The three blocks, in the reference's creation order (one seed: the
+        reference's initial weights)."""
+        self.in_block = _InBlock(self.in_channels, self.num_features)
+        self.f_block = _FBlock(self.num_features, self.num_groups, self.upscale_factor)
+        self.out_block = _OutBlock(self.num_features, self.out_channels, self.upscale_factor)
+
+    def _feature_block(self):
+        """The LR feature extraction block (conv1, prelu1, conv2, prelu2)."""
+        return self.in_block
 
     def _returns_list(self) -> bool:
         return True
@@ -234,6 +249,64 @@ class _DRFBase(BaseNet):
     def _last_conv(self):
         return getattr(self.out_block, f"conv{len(_up_steps(self.upscale_factor)) + 1}")
 
+    def _tail(self, tc, u, pw):
+        """The last conv (F -> out_channels) of the reconstruction, writing the
+        fp32 NCHW output."""
+        b, _, hh, ww, _ = u.shape
+        co = self.out_channels
+        if co == 1:
+            y = torch.empty((b, 1, hh, ww), dtype=torch.float32, device=u.device)
+            F.conv(u, pw(tc), y.view(b, 1, hh, ww, 1), K3, P1, bias=tc.bias)
+        else:
+            tmp = torch.empty((b, 1, hh, ww, co), dtype=torch.float32, device=u.device)
+            y = F.from_view(F.conv(u, pw(tc), tmp, K3, P1, bias=tc.bias))
+        return y
+
+    def _reconstruct(self, t, x, infeat, ffeat, buf, pw, sp):
+        """Frame t's output from in_features and f_features (drf_net.py:46-47):
+        -> (y fp32 NCHW, what the backward needs: tail_in = the last conv's
+        input, ...).  buf(name, t, h, w, c): frame t of a sequence buffer."""
+        f = self.num_features
+        _, _, h, w, _ = infeat.shape
+        feat = F.add(infeat, ffeat, buf("feat", t, h, w, f))  # global residual skip (drf_net.py:46)
+        u, hh, ww, ups_in = feat, h, w, []
+        for j, (conv, st) in enumerate(self._ups()):
+            nxt = buf(f"up{j}", t, hh * st, ww * st, f)
+            F.conv(u, pw(conv, perm_r=st), nxt, K3, P1, bias=conv.bias, y_shuffle=st)
+            ups_in.append(u)
+            u, hh, ww = nxt, hh * st, ww * st
+        return self._tail(self._last_conv(), u, pw), dict(ups_in=ups_in, tail_in=u)
+
+    def _recon_seq_elems(self, HH, WW, h, w) -> int:
+        """Elements per sample and frame of the sequence buffers
+        _reconstruct_backward allocates (the sequence-buffer budget)."""
+        f = self.num_features
+        fe = HH * WW * f  # dup{len(ups)}
+        hh0, ww0 = HH, WW
+        for _, st_ in reversed(self._ups()):
+            hh0, ww0 = hh0 // st_, ww0 // st_
+            fe += hh0 * ww0 * f  # dup{j}
+        return fe
+
+    def _reconstruct_backward(self, bk, t, rc, g):
+        """Frame t's reconstruction backward: weight gradients deferred through
+        bk.wgrad, -> the gradient of the reconstruction's input (a sequence
+        buffer).  bk: the backward's helpers (pw, sp, sbuf, new, wgrad,
+        sp_wgrad, slot, nonpos)."""
+        f = self.num_features
+        u = rc["tail_in"]
+        hh, ww = u.shape[2], u.shape[3]
+        tc = self._last_conv()
+        bk.wgrad(tc, u, g, K3, P1, t)
+        ups = list(zip(self._ups(), rc["ups_in"]))
+        du = F.conv(g, bk.pw(tc, 1), bk.sbuf(f"dup{len(ups)}", t, hh, ww, f), K3, P1)
+        for j in range(len(ups) - 1, -1, -1):
+            (conv, st), uin = ups[j]
+            bk.wgrad(conv, uin, du, K3, P1, t, perm_r=st, dy_shuffle=st)
+            hh, ww = hh // st, ww // st
+            du = F.conv(du, bk.pw(conv, 1, perm_r=st), bk.sbuf(f"dup{j}", t, hh, ww, f), K3, P1, x_shuffle=st)
+        return du
+
     # ------------------------------------------------------------------
     def _run(self, inputs, tape: dict | None):
         frames = self._frames(inputs)
@@ -245,7 +318,7 @@ class _DRFBase(BaseNet):
         H, W = h * s, w * s
         PR = F.ACT_PRELU
         pw, sp = self._packer()
-        ib, fb = self.in_block, self.f_block
+        ib, fb = self._feature_block(), self.f_block
 
         def new(hh, ww, c):
             return torch.empty((b, 1, hh, ww, c), dtype=cd, device=dev)
@@ -320,25 +393,10 @@ class _DRFBase(BaseNet):
             ffeat = X0n[..., f:]  # f_features = next frame's hidden state (drf_net.py:45)
             F.conv(L[..., f:], pw(fb.out_block.conv), ffeat, K1, P0, bias=fb.out_block.conv.bias, act=PR,
                    act_param=fb.out_block.prelu.weight)
-            feat = F.add(X0[..., :f], ffeat, buf("feat", t, h, w, f))  # global residual skip (drf_net.py:46)
-            u, hh, ww, ups_in = feat, h, w, []
-            for j, (conv, st) in enumerate(self._ups()):
-                nxt = buf(f"up{j}", t, hh * st, ww * st, f)
-                F.conv(u, pw(conv, perm_r=st), nxt, K3, P1, bias=conv.bias, y_shuffle=st)
-                ups_in.append(u)
-                u, hh, ww = nxt, hh * st, ww * st
-            tc = self._last_conv()
-            co = self.out_channels
-            if co == 1:
-                y = torch.empty((b, 1, hh, ww), dtype=torch.float32, device=dev)
-                F.conv(u, pw(tc), y.view(b, 1, hh, ww, 1), K3, P1, bias=tc.bias)
-            else:
-                tmp = torch.empty((b, 1, hh, ww, co), dtype=torch.float32, device=dev)
-                y = F.from_view(F.conv(u, pw(tc), tmp, K3, P1, bias=tc.bias))
+            y, rrec = self._reconstruct(t, x, X0[..., :f], ffeat, buf, pw, sp)
             outs.append(y)
             if tape is not None:
-                recs.append(dict(xv=xv, u1=u1, X0=X0, L=L, Hc=Hc, t1s=t1s, t2s=t2s, ffeat=ffeat, ups_in=ups_in,
-                                 tail_in=u))
+                recs.append(dict(xv=xv, u1=u1, X0=X0, L=L, Hc=Hc, t1s=t1s, t2s=t2s, ffeat=ffeat, **rrec))
             X0 = X0n
         if tape is not None:
             tape.update(recs=recs, shape=(b, h, w), packer=(pw, sp), slopes=self._slopes_async())
@@ -351,7 +409,7 @@ class _DRFBase(BaseNet):
         b, h, w = tape["shape"]
         H, W = h * s, w * s
         pw, sp = tape["packer"]
-        ib, fb = self.in_block, self.f_block
+        ib, fb = self._feature_block(), self.f_block
         # PReLUs with a slope <= 0 take the pre-activation backward; so does
         # every PReLU when the slopes are unknown (graph capture)
         if tape.get("slopes") is not None:
@@ -381,11 +439,7 @@ class _DRFBase(BaseNet):
         Kg = T
         if seq:
             HH0, WW0 = recs[0]["tail_in"].shape[2], recs[0]["tail_in"].shape[3]
-            fe = HH0 * WW0 * f  # dup{len(ups)}
-            hh0, ww0 = HH0, WW0
-            for _, st_ in reversed(self._ups()):
-                hh0, ww0 = hh0 // st_, ww0 // st_
-                fe += hh0 * ww0 * f  # dup{j}
+            fe = self._recon_seq_elems(HH0, WW0, h, w)
             fe += (2 * G + 2) * h * w * f + h * w * 4 * f  # gout, dL ((G + 1) f), dt1_*, gin, du_u1
             fe += (2 * G - 1) * H * W * f  # dHc (G f), dt2_*
             frame_bytes = fe * b * torch.empty((), dtype=cd).element_size()
@@ -569,6 +623,8 @@ class _DRFBase(BaseNet):
                 return F.prelu_bwd(pre(), dy, pr.weight, out, da_, acc_, dy2=dy2, pre=True, slot=sl_)
             return F.prelu_bwd(y, dy, pr.weight, out, da_, acc_, dy2=dy2, slot=sl_)
 
+        bk = types.SimpleNamespace(pw=pw, sp=sp, sbuf=sbuf, new=new, wgrad=wgrad, sp_wgrad=sp_wgrad, slot=slot,
+                                   nonpos=nonpos)
         co = self.out_channels
         HH, WW = recs[0]["tail_in"].shape[2], recs[0]["tail_in"].shape[3]
         gfull = [gys[t] if t < len(gys) and gys[t] is not None else
@@ -578,19 +634,9 @@ class _DRFBase(BaseNet):
         for t in range(T - 1, -1, -1):
             cur[0] = t
             rc = recs[t]
-            u = rc["tail_in"]
-            hh, ww = u.shape[2], u.shape[3]
             g = GV[t * b:(t + 1) * b]
-            tc = self._last_conv()
-            wgrad(tc, u, g, K3, P1, t)
-            ups = list(zip(self._ups(), rc["ups_in"]))
-            du = F.conv(g, pw(tc, 1), sbuf(f"dup{len(ups)}", t, hh, ww, f), K3, P1)
-            for j in range(len(ups) - 1, -1, -1):
-                (conv, st), uin = ups[j]
-                wgrad(conv, uin, du, K3, P1, t, perm_r=st, dy_shuffle=st)
-                hh, ww = hh // st, ww // st
-                du = F.conv(du, pw(conv, 1, perm_r=st), sbuf(f"dup{j}", t, hh, ww, f), K3, P1, x_shuffle=st)
-            gfeat = du  # grad of features = in_features + f_features
+            # grad of the reconstruction's input (DRF: features = in_features + f_features)
+            gfeat = self._reconstruct_backward(bk, t, rc, g)
             L, Hc, X0 = rc["L"], rc["Hc"], rc["X0"]
             # f_block out: f_features feeds the skip and the next frame's hidden state
             gout = prelu(rc["ffeat"], gfeat, fb.out_block.prelu, sbuf("gout", t, h, w, f), dy2=d_hidden,
@@ -717,8 +763,12 @@ class _DRFBase(BaseNet):
                 d_hidden = None
             else:
                 d_hidden = dX0[..., f:]
-            gin = prelu(X0[..., :f], gfeat, ib.prelu2, sbuf("gin", t, h, w, f), dy2=dX0[..., :f],
-                        pre=lambda: F.conv(rc["u1"], pw(ib.conv2), new(h, w, f), K1, P0, bias=ib.conv2.bias))
+            if self._FEATURE_SKIP:
+                gin = prelu(X0[..., :f], gfeat, ib.prelu2, sbuf("gin", t, h, w, f), dy2=dX0[..., :f],
+                            pre=lambda: F.conv(rc["u1"], pw(ib.conv2), new(h, w, f), K1, P0, bias=ib.conv2.bias))
+            else:  # in_features reach the output through the feedback block alone
+                gin = prelu(X0[..., :f], dX0[..., :f], ib.prelu2, sbuf("gin", t, h, w, f),
+                            pre=lambda: F.conv(rc["u1"], pw(ib.conv2), new(h, w, f), K1, P0, bias=ib.conv2.bias))
             wgrad(ib.conv2, rc["u1"], gin, K1, P0, t)
             du1 = sbuf("du_u1", t, h, w, 4 * f)
             wi2 = pw(ib.conv2, 1)

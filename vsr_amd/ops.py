@@ -20,6 +20,9 @@ converts in and out (the fused generators avoid that).
   vsrk::batch_norm(x, weight, bias, stats, training, relu)
       nn.BatchNorm3d (+ nn.ReLU): statistics (running statistics updated in
       training), then the normalisation with its autograd formula
+  vsrk::upsample2d(x, scale, mode, align_corners)
+      F.interpolate / nn.Upsample by an integer factor, 'bilinear' or
+      'bicubic', on (N, C, H, W); the backward is the adjoint gather kernel
   vsrk::duf_dynfilter(x, logits, residual, k, r)   DUF dynamic upsampling
   vsrk::loss(out, target, kind, param)             L1 / MSE / Huber / Charbonnier
   vsrk::psnr(out, target, mean, std, max_value, denormalize) -> per-sample
@@ -273,6 +276,60 @@ def _bn_bwd(ctx, gy):
 
 
 batch_norm.register_autograd(_bn_bwd, setup_context=_bn_setup)
+
+
+# -------------------------------------------------------------- upsample --
+def _updtype(x: Tensor) -> Tensor:
+    xc = x.contiguous()
+    return xc if xc.dtype in (torch.float32, torch.bfloat16, torch.float16) else xc.float()
+
+
+@torch.library.custom_op("vsrk::upsample2d", mutates_args=())
+def upsample2d(x: Tensor, scale: int, mode: str, align_corners: bool) -> Tensor:
+    """F.interpolate(x, scale_factor=scale, mode=mode, align_corners=align_corners)
+    for (N, C, H, W) x, mode 'bilinear' or 'bicubic' (srfb_net.py:47, bicubic.py:15)."""
+    if x.dim() != 4:
+        raise ValueError(f"vsrk::upsample2d expects (N, C, H, W), got {tuple(x.shape)}")
+    xc = _updtype(x)
+    n, c, h, w = xc.shape
+    y = torch.empty((n, c, h * scale, w * scale), dtype=xc.dtype, device=x.device)
+    F.upsample2d(xc, y, mode, align_corners, scale)
+    return y if y.dtype == x.dtype else y.to(x.dtype)
+
+
+@upsample2d.register_fake
+def _(x, scale, mode, align_corners):
+    n, c, h, w = x.shape
+    return x.new_empty((n, c, h * scale, w * scale))
+
+
+@torch.library.custom_op("vsrk::upsample2d_backward", mutates_args=())
+def upsample2d_backward(grad: Tensor, scale: int, mode: str, align_corners: bool) -> Tensor:
+    """grad_x of vsrk::upsample2d: the adjoint applied to grad (N, C, scale*H, scale*W)."""
+    gc = _updtype(grad)
+    n, c, hh, ww = gc.shape
+    gx = torch.empty((n, c, hh // scale, ww // scale), dtype=gc.dtype, device=grad.device)
+    F.upsample2d_bwd(gc, gx, mode, align_corners, scale)
+    return gx if gx.dtype == grad.dtype else gx.to(grad.dtype)
+
+
+@upsample2d_backward.register_fake
+def _(grad, scale, mode, align_corners):
+    n, c, hh, ww = grad.shape
+    return grad.new_empty((n, c, hh // scale, ww // scale))
+
+
+def _up_setup(ctx, inputs, output):
+    _, scale, mode, align_corners = inputs
+    ctx.cfg = (scale, mode, align_corners)
+
+
+def _up_bwd(ctx, grad):
+    scale, mode, align_corners = ctx.cfg
+    return upsample2d_backward(grad, scale, mode, align_corners), None, None, None
+
+
+upsample2d.register_autograd(_up_bwd, setup_context=_up_setup)
 
 
 # ----------------------------------------------------------- DUF filter --
