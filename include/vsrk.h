@@ -451,6 +451,72 @@ int vsrk_upsample2d_fwd(int32_t dtype, const void* x, int64_t planes, int32_t h,
 int vsrk_upsample2d_bwd(int32_t dtype, const void* gy, int64_t planes, int32_t h, int32_t w, int32_t r, int32_t mode,
                         int32_t align_corners, int32_t accumulate, void* gx, void* stream);
 
+/* Flow warping, the reference's STN (frvsr_net.py:196-240): F.grid_sample(img,
+ * mesh + flow, 'bilinear', padding_mode, align_corners) with the mesh
+ * np.linspace(-1, 1, size) per axis (rounded to fp32 as the reference's mesh
+ * tensor is; -1 when size = 1) and the flow added in NORMALISED units:
+ *   out(n,y,x,c) = bilinear sample of img(n,:,:,c) at the pixel position of
+ *                  (mesh_x(x) + flow(n,0,y,x), mesh_y(y) + flow(n,1,y,x)),
+ * un-normalised as torch does for align_corners (0: ((g+1) size - 1) / 2,
+ * 1: (g+1)/2 (size-1)).  padding_mode 0 = 'zeros' (corners outside the image
+ * read 0), 1 = 'border' (the position is clipped to [0, size-1]).
+ * img is an (n, 1, h, w, c) view of fp32 / bf16 / fp16; flow is (n, 2, h, w)
+ * fp32 contiguous (u then v) and is never rounded to the image type.  The
+ * mesh value comes from the integer pixel index; position and blend are fp32
+ * arithmetic, operation for operation torch's.
+ * out (and gout) is a plain view of img's dtype.  s2d = 1: (n, 1, h, w, c).
+ * s2d = r > 1: the store is fused with the reference's SpaceToDepth(r)
+ * (frvsr_net.py:178-193): out is (n, 1, h/r, w/r, r*r*c), warped pixel
+ * (y, x), channel c' goes to pixel (y/r, x/r), channel ((y%r)*r + x%r)*c + c'
+ * -- e.g. a channel slice of the SR net's concat input.  The reference's
+ * order is c'*r*r + (y%r)*r + x%r: equal for c = 1; for c > 1 permute the
+ * consuming conv's input channels.
+ * vsrk_flow_warp_bwd: gflow(n,0..1,y,x) [+]= sum_c gout(n,y,x,c) * d out /
+ * d flow, torch's grid_sampler_2d gradient with respect to the grid
+ * (including the factor 0 where 'border' clipped the position).  One thread
+ * owns one pixel: no atomics, bitwise reproducible.  There is NO image
+ * gradient at this level: the reference warps input data and a detached
+ * estimate only (frvsr_net.py:49,55).
+ * flow_up = 1: the flow has the image's resolution.  flow_up = r > 1: flow is
+ * (n, 2, h/r, w/r) and each pixel's (u, v) is its bilinear x r, align_corners
+ * = 1 interpolation (vsrk_upsample2d_fwd's taps and blend order), computed in
+ * the kernel: the reference's interpolate(lr_flow, r) -> warp (frvsr_net.py:
+ * 48-49) without the two fp32 HR planes.  gflow stays (n, 2, h, w), the
+ * gradient with respect to the INTERPOLATED flow: vsrk_upsample2d_bwd takes it
+ * down to the coarse flow. */
+int vsrk_flow_warp_fwd(const vsrk_tensor5* img, const float* flow, int32_t flow_up, const vsrk_tensor5* out,
+                       int32_t s2d, int32_t padding_mode, int32_t align_corners, void* stream);
+int vsrk_flow_warp_bwd(const vsrk_tensor5* img, const float* flow, int32_t flow_up, const vsrk_tensor5* gout,
+                       int32_t s2d, int32_t padding_mode, int32_t align_corners, int32_t accumulate, float* gflow,
+                       void* stream);
+
+/* nn.MaxPool2d(2) on channels-last (n, 1, h, w, c) views (frvsr_net.py:127):
+ * y is (n, 1, h/2, w/2, c), odd sizes floor.  On exact ties the first maximum
+ * in row-major window order wins and a NaN wins over what precedes it, as in
+ * torch's CPU kernel.  The backward recomputes the arg-max from the saved
+ * input x and writes all of gx (zeros off the arg-max and in an odd last row
+ * or column).  16-byte accesses along the channel axis where c, the base
+ * pointers and the strides allow; one element per lane otherwise. */
+int vsrk_max_pool2x2_fwd(const vsrk_tensor5* x, const vsrk_tensor5* y, void* stream);
+int vsrk_max_pool2x2_bwd(const vsrk_tensor5* x, const vsrk_tensor5* gy, const vsrk_tensor5* gx, void* stream);
+
+/* vsrk_upsample2d_* (bilinear) on channels-last views: x (n, 1, h, w, c) ->
+ * y (n, 1, r*h, r*w, c), F.interpolate(scale_factor=r, mode='bilinear',
+ * align_corners) -- FNet's BilinerUp(2) (frvsr_net.py:135,169-175).  Same tap
+ * arithmetic as the plane kernels; accumulate = 1: y += Up(x) / gx +=
+ * Up^T(gy); the adjoint is a fixed-order gather (bitwise reproducible).
+ * 16-byte accesses along the channel axis as for the pool. */
+int vsrk_upsample_cl_fwd(const vsrk_tensor5* x, const vsrk_tensor5* y, int32_t r, int32_t align_corners,
+                         int32_t accumulate, void* stream);
+int vsrk_upsample_cl_bwd(const vsrk_tensor5* gy, const vsrk_tensor5* gx, int32_t r, int32_t align_corners,
+                         int32_t accumulate, void* stream);
+
+/* nn.Tanh on views of one shape and dtype (frvsr_net.py:143): y = tanh(x);
+ * dx = dy * (1 - y^2) from the forward OUTPUT y.  y may alias x, dx may
+ * alias dy. */
+int vsrk_tanh_fwd(const vsrk_tensor5* x, const vsrk_tensor5* y, void* stream);
+int vsrk_tanh_bwd(const vsrk_tensor5* y, const vsrk_tensor5* dy, const vsrk_tensor5* dx, void* stream);
+
 const char* vsrk_last_error(void);
 const char* vsrk_version(void);
 

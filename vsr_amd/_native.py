@@ -136,6 +136,14 @@ _SIGS = {
     "vsrk_ssim3d": (C.c_int, [_P, _P] + [C.c_int32] * 6 + [C.c_float] * 3 + [_P, _P, _P, C.c_size_t, _P]),
     "vsrk_upsample2d_fwd": (C.c_int, [C.c_int32, _P, C.c_int64] + [C.c_int32] * 6 + [_P, _P]),
     "vsrk_upsample2d_bwd": (C.c_int, [C.c_int32, _P, C.c_int64] + [C.c_int32] * 6 + [_P, _P]),
+    "vsrk_flow_warp_fwd": (C.c_int, [_T5, _P, C.c_int32, _T5, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "vsrk_flow_warp_bwd": (C.c_int, [_T5, _P, C.c_int32, _T5, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "vsrk_max_pool2x2_fwd": (C.c_int, [_T5, _T5, _P]),
+    "vsrk_max_pool2x2_bwd": (C.c_int, [_T5, _T5, _T5, _P]),
+    "vsrk_upsample_cl_fwd": (C.c_int, [_T5, _T5, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "vsrk_upsample_cl_bwd": (C.c_int, [_T5, _T5, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "vsrk_tanh_fwd": (C.c_int, [_T5, _T5, _P]),
+    "vsrk_tanh_bwd": (C.c_int, [_T5, _T5, _T5, _P]),
     "vsrk_last_error": (C.c_char_p, []),
     "vsrk_version": (C.c_char_p, []),
 }

@@ -147,6 +147,24 @@ __global__ void add_kernel(View a, View b, View o, int64_t total) {
   reinterpret_cast<T*>(o.ptr)[view_off(o, n, d, h, w, c)] = from_f32<T>(av + bv);
 }
 
+// nn.Tanh on a view (FNet's flow head, frvsr_net.py:143): BWD = 0 y = tanh(a),
+// BWD = 1 out = b * (1 - a^2) with a the forward output and b its gradient
+template <typename T, int BWD>
+__global__ void tanh_kernel(View a, View b, View o, int64_t total) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int c = idx % a.c;
+  int n, d, h, w;
+  decode_voxel(idx / a.c, a, n, d, h, w);
+  const float av = to_f32<T>(reinterpret_cast<const T*>(a.ptr)[view_off(a, n, d, h, w, c)]);
+  float r;
+  if (BWD)
+    r = to_f32<T>(reinterpret_cast<const T*>(b.ptr)[view_off(b, n, d, h, w, c)]) * (1.f - av * av);
+  else
+    r = tanhf(av);
+  reinterpret_cast<T*>(o.ptr)[view_off(o, n, d, h, w, c)] = from_f32<T>(r);
+}
+
 // ---- losses ----
 __device__ __forceinline__ float loss_val(int kind, float p, float d) {
   const float a = fabsf(d);
@@ -368,6 +386,41 @@ extern "C" int vsrk_add(const vsrk_tensor5* a, const vsrk_tensor5* b, const vsrk
     add_kernel<float><<<(int)ceil_div64(total, 256), 256, 0, s>>>(make_view(a), make_view(b), make_view(out), total);
   VSRK_LAUNCH_CHECK("add");
   return VSRK_OK;
+}
+
+static bool same_geometry(const vsrk_tensor5* a, const vsrk_tensor5* b) {
+  return a->dtype == b->dtype && a->n == b->n && a->d == b->d && a->h == b->h && a->w == b->w && a->c == b->c &&
+         a->shuffle == b->shuffle;
+}
+
+template <int BWD>
+static int launch_tanh(const char* name, const vsrk_tensor5* a, const vsrk_tensor5* b, const vsrk_tensor5* o,
+                       void* stream) {
+  VSRK_CHECK(a && b && o && a->ptr && b->ptr && o->ptr, "%s: null argument", name);
+  VSRK_CHECK(a->dtype == VSRK_F32 || a->dtype == VSRK_BF16 || a->dtype == VSRK_F16, "%s: unknown dtype %d", name,
+             a->dtype);
+  VSRK_CHECK(same_geometry(a, b) && same_geometry(a, o), "%s: views differ in shape or dtype", name);
+  const int64_t total = nvox(a) * a->c;
+  VSRK_CHECK(total >= 1 && total <= ((int64_t)1 << 39), "%s: empty or too large (%lld elements)", name,
+             (long long)total);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)ceil_div64(total, 256));
+  if (a->dtype == VSRK_BF16)
+    tanh_kernel<bf16, BWD><<<grid, 256, 0, s>>>(make_view(a), make_view(b), make_view(o), total);
+  else if (a->dtype == VSRK_F16)
+    tanh_kernel<f16, BWD><<<grid, 256, 0, s>>>(make_view(a), make_view(b), make_view(o), total);
+  else
+    tanh_kernel<float, BWD><<<grid, 256, 0, s>>>(make_view(a), make_view(b), make_view(o), total);
+  VSRK_LAUNCH_CHECK(name);
+  return VSRK_OK;
+}
+
+extern "C" int vsrk_tanh_fwd(const vsrk_tensor5* x, const vsrk_tensor5* y, void* stream) {
+  return launch_tanh<0>("tanh_fwd", x, x, y, stream);
+}
+
+extern "C" int vsrk_tanh_bwd(const vsrk_tensor5* y, const vsrk_tensor5* dy, const vsrk_tensor5* dx, void* stream) {
+  return launch_tanh<1>("tanh_bwd", y, dy, dx, stream);
 }
 
 extern "C" size_t vsrk_loss_workspace_size(int64_t count) { return 1024 * sizeof(double); }

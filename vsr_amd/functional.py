@@ -522,6 +522,107 @@ def upsample2d_bwd(gy: torch.Tensor, gx: torch.Tensor, mode, align_corners: bool
     return _upsample(_lib().vsrk_upsample2d_bwd, "upsample2d_bwd", gx, gy, gy, gx, mode, align_corners, r, accumulate)
 
 
+def upsample_cl(x: torch.Tensor, y: torch.Tensor, r: int, align_corners: bool,
+                accumulate: bool = False) -> torch.Tensor:
+    """y [+]= bilinear x r of channels-last x (N, 1, h, w, C) -> y (N, 1, r*h,
+    r*w, C) views of one dtype (F.interpolate's taps; fp32 arithmetic)."""
+    xv, yv = N.t5(x), N.t5(y)
+    N.check(_lib().vsrk_upsample_cl_fwd(C.byref(xv), C.byref(yv), int(r), 1 if align_corners else 0,
+                                        1 if accumulate else 0, N.stream_ptr(x.device)), "upsample_cl_fwd")
+    return y
+
+
+def upsample_cl_bwd(gy: torch.Tensor, gx: torch.Tensor, r: int, align_corners: bool,
+                    accumulate: bool = False) -> torch.Tensor:
+    """gx [+]= the adjoint of upsample_cl applied to gy (N, 1, r*h, r*w, C) ->
+    gx (N, 1, h, w, C): a fixed-order gather, bitwise reproducible."""
+    gv, xv = N.t5(gy), N.t5(gx)
+    N.check(_lib().vsrk_upsample_cl_bwd(C.byref(gv), C.byref(xv), int(r), 1 if align_corners else 0,
+                                        1 if accumulate else 0, N.stream_ptr(gy.device)), "upsample_cl_bwd")
+    return gx
+
+
+def max_pool2x2(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """y = nn.MaxPool2d(2) of channels-last x (N, 1, h, w, C) -> (N, 1, h//2, w//2, C)."""
+    xv, yv = N.t5(x), N.t5(y)
+    N.check(_lib().vsrk_max_pool2x2_fwd(C.byref(xv), C.byref(yv), N.stream_ptr(x.device)), "max_pool2x2_fwd")
+    return y
+
+
+def max_pool2x2_bwd(x: torch.Tensor, gy: torch.Tensor, gx: torch.Tensor) -> torch.Tensor:
+    """gx = gy routed to each window's arg-max (recomputed from the pool's
+    input x; the first maximum on ties), zeros elsewhere."""
+    xv, gv, ov = N.t5(x), N.t5(gy), N.t5(gx)
+    N.check(_lib().vsrk_max_pool2x2_bwd(C.byref(xv), C.byref(gv), C.byref(ov), N.stream_ptr(x.device)),
+            "max_pool2x2_bwd")
+    return gx
+
+
+def tanh(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """y = tanh(x) on views of one shape and dtype (y may be x)."""
+    xv, yv = N.t5(x), N.t5(y)
+    N.check(_lib().vsrk_tanh_fwd(C.byref(xv), C.byref(yv), N.stream_ptr(x.device)), "tanh_fwd")
+    return y
+
+
+def tanh_bwd(y: torch.Tensor, dy: torch.Tensor, dx: torch.Tensor) -> torch.Tensor:
+    """dx = dy * (1 - y^2) from the forward output y (dx may be dy)."""
+    yv, gv, ov = N.t5(y), N.t5(dy), N.t5(dx)
+    N.check(_lib().vsrk_tanh_bwd(C.byref(yv), C.byref(gv), C.byref(ov), N.stream_ptr(y.device)), "tanh_bwd")
+    return dx
+
+
+PADDING_MODES = {"zeros": 0, "border": 1}
+
+
+def _flow_arg(what: str, flow: torch.Tensor, img: torch.Tensor, up: int = 1) -> None:
+    n, _, h, w, _ = img.shape
+    if up < 1 or h % up or w % up:
+        raise ValueError(f"{what}: flow_up {up} does not divide the image {h} x {w}")
+    if tuple(flow.shape) != (n, 2, h // up, w // up):
+        raise ValueError(f"{what}: flow must be {(n, 2, h // up, w // up)} for an image {tuple(img.shape)}"
+                         f"{f' and flow_up {up}' if up > 1 else ''}, got {tuple(flow.shape)}")
+    if flow.dtype != torch.float32 or not flow.is_contiguous():
+        raise TypeError(f"{what}: the flow is contiguous fp32 (it is never rounded to the image type)")
+    if flow.device != img.device:
+        raise RuntimeError(f"{what}: flow and image are on different devices")
+
+
+def flow_warp(img: torch.Tensor, flow: torch.Tensor, out: torch.Tensor, padding_mode, align_corners: bool,
+              s2d: int = 1, flow_up: int = 1) -> torch.Tensor:
+    """out = F.grid_sample(img, mesh + flow, 'bilinear', padding_mode,
+    align_corners) on the reference's linspace(-1, 1) mesh: img (N, 1, h, w, C)
+    channels-last, flow (N, 2, h, w) fp32 in normalised units (u, v).  out is
+    (N, 1, h, w, C), or with s2d = r the space-to-depth image (N, 1, h/r, w/r,
+    r*r*C) (vsrk_flow_warp_fwd), e.g. a channel slice of a wider buffer.
+    flow_up = r: flow is (N, 2, h/r, w/r) and is interpolated bilinearly
+    (align_corners=True) inside the kernel."""
+    pm = PADDING_MODES[padding_mode] if isinstance(padding_mode, str) else int(padding_mode)
+    _flow_arg("flow_warp_fwd", flow, img, int(flow_up))
+    iv, ov = N.t5(img), N.t5(out)
+    N.check(_lib().vsrk_flow_warp_fwd(C.byref(iv), flow.data_ptr(), int(flow_up), C.byref(ov), int(s2d), pm,
+                                      1 if align_corners else 0, N.stream_ptr(img.device)), "flow_warp_fwd")
+    return out
+
+
+def flow_warp_bwd(img: torch.Tensor, flow: torch.Tensor, gout: torch.Tensor, gflow: torch.Tensor, padding_mode,
+                  align_corners: bool, s2d: int = 1, accumulate: bool = False, flow_up: int = 1) -> torch.Tensor:
+    """gflow (N, 2, h, w) fp32 [+]= the gradient of flow_warp with respect to
+    the flow, given gout in out's layout.  A gather, one thread per pixel:
+    bitwise reproducible.  (The image gets no gradient: vsrk_flow_warp_bwd.)
+    With flow_up = r the positions come from the coarse flow as in flow_warp
+    and gflow is the gradient of the interpolated flow: upsample2d_bwd(gflow,
+    ..., 'bilinear', True, r) takes it down to the coarse one."""
+    pm = PADDING_MODES[padding_mode] if isinstance(padding_mode, str) else int(padding_mode)
+    _flow_arg("flow_warp_bwd", flow, img, int(flow_up))
+    _flow_arg("flow_warp_bwd", gflow, img)
+    iv, gv = N.t5(img), N.t5(gout)
+    N.check(_lib().vsrk_flow_warp_bwd(C.byref(iv), flow.data_ptr(), int(flow_up), C.byref(gv), int(s2d), pm,
+                                      1 if align_corners else 0, 1 if accumulate else 0, gflow.data_ptr(),
+                                      N.stream_ptr(img.device)), "flow_warp_bwd")
+    return gflow
+
+
 def loss_fwd(kind: int, param: float, out: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     """Mean-reduced loss of two fp32 tensors -> device scalar."""
     lib = _lib()

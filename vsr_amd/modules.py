@@ -10,10 +10,15 @@ its convolutions / batch norms on MI355X:
   nn.Conv2d / nn.Conv3d (kernel 1 or 3 in h, w; stride 1; zero padding)  -> HipConv2d / HipConv3d
   nn.Conv2d(k, stride s, padding p), k <= p + 2s, p <= s (DRF's down
       projections, drf_net.py:93,100)                                   -> HipConv2d (sub-pixel form)
-  nn.ConvTranspose2d(k, s, p) (DRF's up projections, drf_net.py:81,86)  -> HipConvTranspose2d
+  nn.ConvTranspose2d(k, s, p) (DRF's up projections, drf_net.py:81,86),
+      output_padding 0 or s - k + 2p (FRVSR's tail, frvsr_net.py:84,86)   -> HipConvTranspose2d
+  nn.MaxPool2d(2) (FRVSR's FNet, frvsr_net.py:127)                      -> HipMaxPool2d
   nn.BatchNorm3d (duf_net.py:116,198,201)                               -> HipBatchNorm3d
   nn.Upsample(scale_factor=r, mode='bilinear' | 'bicubic'), integer r (or a
       pair of equal integers), 4-D input (bicubic.py:15)                -> HipUpsample
+
+``STN`` is the reference's flow-warp module (frvsr_net.py:196-226) by name and
+signature, on vsrk::flow_warp; it has no torch.nn counterpart to swap.
 
 Other nn.Upsample forms (nearest, trilinear, size=, a non-integer scale) are
 left as they are.  Activations, PixelShuffle and tensor plumbing stay torch ops.  The fused
@@ -106,6 +111,67 @@ class HipUpsample(nn.Upsample):
         return torch.ops.vsrk.upsample2d(input, r, self.mode, bool(self.align_corners))
 
 
+def _pair(v) -> tuple:
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def _pool2x2(m: nn.MaxPool2d) -> bool:
+    """nn.MaxPool2d(2): kernel 2, stride 2 (or the default: the kernel), no
+    padding, dilation, ceil_mode or indices."""
+    stride = m.kernel_size if m.stride is None else m.stride
+    return (_pair(m.kernel_size) == (2, 2) and _pair(stride) == (2, 2) and _pair(m.padding) == (0, 0)
+            and _pair(m.dilation) == (1, 1) and not m.ceil_mode and not m.return_indices)
+
+
+class HipMaxPool2d(nn.MaxPool2d):
+    """nn.MaxPool2d(2) on vsrk::max_pool2x2 for 4-D inputs (frvsr_net.py:127);
+    any other configuration or rank runs nn.MaxPool2d's own forward."""
+
+    def forward(self, input):
+        if input.dim() != 4 or not _pool2x2(self):
+            return super().forward(input)
+        return torch.ops.vsrk.max_pool2x2(input)
+
+
+class STN(nn.Module):
+    """The reference's spatial transformer (frvsr_net.py:196-240) on
+    vsrk::flow_warp: ``forward(inputs, u, v)`` samples ``inputs`` (N, C, H, W)
+    bilinearly at mesh + (u, v), the mesh being linspace(-1, 1) per axis and
+    the flow in normalised units; ``normalize=True`` takes a flow in pixels
+    and divides it by half the image size as the reference does.  grid_sample
+    runs with its default align_corners=False, as in the reference.  The
+    gradient goes to u and v only."""
+
+    def __init__(self, mode="bilinear", padding_mode="zeros", normalize=False):
+        super().__init__()
+        self.mode = mode
+        self.padding_mode = padding_mode
+        self.norm = normalize
+
+    def forward(self, inputs, u, v):
+        if self.mode != "bilinear":
+            raise NotImplementedError(f"STN: sampling mode {self.mode!r} (the warp kernel is bilinear)")
+        if self.padding_mode not in ("zeros", "border"):
+            raise NotImplementedError(f"STN: padding_mode {self.padding_mode!r} ('zeros' or 'border')")
+        if self.norm:
+            h, w = inputs.shape[-2:]
+            u = u / w * 2
+            v = v / h * 2
+        return torch.ops.vsrk.flow_warp(inputs, u, v, self.padding_mode, False)
+
+
+def _deconv_output_padding_ok(m: nn.ConvTranspose2d) -> bool:
+    """The sub-pixel form writes exactly s*h rows: torch's size when
+    output_padding = s - k + 2p (frvsr_net.py:84,86: (3, 2, 1) with 1).
+    output_padding = 0 is accepted for every (k, s, p) too, as it always was:
+    that is right where s - k + 2p = 0 (every DRF deconv) and a KNOWN WRONG
+    SIZE otherwise -- (3, 2, 1) with 0 is 2h - 1 rows in torch, 2h here.  Kept
+    so that every module converted so far converts the same way; a later
+    change can accept s - k + 2p alone."""
+    k, s, p = m.kernel_size[0], m.stride[0], m.padding[0]
+    return m.output_padding in ((0, 0), (s - k + 2 * p,) * 2)
+
+
 def _convert(m: nn.Module) -> nn.Module | None:
     if type(m) is nn.Conv2d:
         if _supported_conv(m):
@@ -117,10 +183,12 @@ def _convert(m: nn.Module) -> nn.Module | None:
             return None
     elif type(m) is nn.Conv3d and _supported_conv(m):
         new = HipConv3d.__new__(HipConv3d)
-    elif (type(m) is nn.ConvTranspose2d and m.groups == 1 and m.output_padding == (0, 0)
+    elif (type(m) is nn.ConvTranspose2d and m.groups == 1 and _deconv_output_padding_ok(m)
           and m.kernel_size[0] == m.kernel_size[1] and m.stride[0] == m.stride[1]
           and _subpixel_ok(m.kernel_size[0], m.stride[0], m.padding[0])):
         new = HipConvTranspose2d.__new__(HipConvTranspose2d)
+    elif type(m) is nn.MaxPool2d and _pool2x2(m):
+        new = HipMaxPool2d.__new__(HipMaxPool2d)
     elif type(m) is nn.BatchNorm3d:
         new = HipBatchNorm3d.__new__(HipBatchNorm3d)
     elif (type(m) is nn.Upsample and m.mode in ("bilinear", "bicubic") and m.size is None

@@ -5,6 +5,7 @@ from .bicubic import Bicubic
 from .drf_net import DRFNet, DRFSISRNet
 from .duf_net import DUFNet
 from .edsr_net import EDSRNet
+from .frvsr_net import FRVSRNet
 from .srfb_net import SRFBNet
 
-__all__ = ["BaseNet", "EDSRNet", "DUFNet", "DRFNet", "DRFSISRNet", "SRFBNet", "Bicubic"]
+__all__ = ["BaseNet", "EDSRNet", "DUFNet", "DRFNet", "DRFSISRNet", "SRFBNet", "Bicubic", "FRVSRNet"]

@@ -23,6 +23,11 @@ converts in and out (the fused generators avoid that).
   vsrk::upsample2d(x, scale, mode, align_corners)
       F.interpolate / nn.Upsample by an integer factor, 'bilinear' or
       'bicubic', on (N, C, H, W); the backward is the adjoint gather kernel
+  vsrk::flow_warp(img, u, v, padding_mode, align_corners)
+      F.grid_sample on the reference STN's mesh plus a flow; the backward is
+      the flow gradient (none for the image)
+  vsrk::max_pool2x2(x)
+      nn.MaxPool2d(2) on (N, C, H, W)
   vsrk::duf_dynfilter(x, logits, residual, k, r)   DUF dynamic upsampling
   vsrk::loss(out, target, kind, param)             L1 / MSE / Huber / Charbonnier
   vsrk::psnr(out, target, mean, std, max_value, denormalize) -> per-sample
@@ -330,6 +335,117 @@ def _up_bwd(ctx, grad):
 
 
 upsample2d.register_autograd(_up_bwd, setup_context=_up_setup)
+
+
+# ------------------------------------------------------------- flow warp --
+def _flow(u: Tensor, v: Tensor) -> Tensor:
+    """(N, H, W) u and v -> (N, 2, H, W) fp32 contiguous."""
+    return torch.stack([u, v], dim=1).float().contiguous()
+
+
+def _warp_check(img: Tensor, u: Tensor, v: Tensor) -> None:
+    if img.dim() != 4:
+        raise ValueError(f"vsrk::flow_warp expects an (N, C, H, W) image, got {tuple(img.shape)}")
+    want = (img.shape[0], img.shape[2], img.shape[3])
+    if tuple(u.shape) != want or tuple(v.shape) != want:
+        raise ValueError(f"vsrk::flow_warp: u and v must be {want}, got {tuple(u.shape)} and {tuple(v.shape)}")
+
+
+@torch.library.custom_op("vsrk::flow_warp", mutates_args=())
+def flow_warp(img: Tensor, u: Tensor, v: Tensor, padding_mode: str, align_corners: bool) -> Tensor:
+    """F.grid_sample(img, mesh + stack([u, v], -1), 'bilinear', padding_mode,
+    align_corners) on the mesh linspace(-1, 1) per axis: the reference's STN
+    (frvsr_net.py:196-240).  img (N, C, H, W); u, v (N, H, W) in normalised
+    units, kept in fp32 whatever img's dtype.  Differentiable in u and v only."""
+    _warp_check(img, u, v)
+    iv = _to_cl(img, img.dtype)
+    ov = _empty_cl(iv.shape[:-1], iv.shape[-1], img.dtype, img.device)
+    F.flow_warp(iv, _flow(u, v), ov, padding_mode, align_corners)
+    return _from_cl(ov, True, img.dtype)
+
+
+@flow_warp.register_fake
+def _(img, u, v, padding_mode, align_corners):
+    return img.new_empty(img.shape)
+
+
+@torch.library.custom_op("vsrk::flow_warp_backward", mutates_args=())
+def flow_warp_backward(grad: Tensor, img: Tensor, u: Tensor, v: Tensor, padding_mode: str,
+                       align_corners: bool) -> Tuple[Tensor, Tensor]:
+    """(grad_u, grad_v) of vsrk::flow_warp: the gather of vsrk_flow_warp_bwd."""
+    iv, gv = _to_cl(img, img.dtype), _to_cl(grad, img.dtype)
+    gf = torch.empty((img.shape[0], 2, img.shape[2], img.shape[3]), dtype=torch.float32, device=img.device)
+    F.flow_warp_bwd(iv, _flow(u, v), gv, gf, padding_mode, align_corners)
+    return gf[:, 0].to(u.dtype, copy=True), gf[:, 1].to(v.dtype, copy=True)  # op outputs may not share storage
+
+
+@flow_warp_backward.register_fake
+def _(grad, img, u, v, padding_mode, align_corners):
+    return u.new_empty(u.shape), v.new_empty(v.shape)
+
+
+def _warp_setup(ctx, inputs, output):
+    img, u, v, padding_mode, align_corners = inputs
+    if ctx.needs_input_grad[0]:
+        raise NotImplementedError(
+            "vsrk::flow_warp has no gradient with respect to the image: the kernels give the flow gradient only "
+            "(FRVSR warps input frames and a detached estimate); detach the image")
+    ctx.save_for_backward(img, u, v)
+    ctx.cfg = (padding_mode, align_corners)
+
+
+def _warp_bwd(ctx, grad):
+    img, u, v = ctx.saved_tensors
+    padding_mode, align_corners = ctx.cfg
+    gu, gv = flow_warp_backward(grad.contiguous(), img, u, v, padding_mode, align_corners)
+    return None, gu, gv, None, None
+
+
+flow_warp.register_autograd(_warp_bwd, setup_context=_warp_setup)
+
+
+# -------------------------------------------------------------- max pool --
+@torch.library.custom_op("vsrk::max_pool2x2", mutates_args=())
+def max_pool2x2(x: Tensor) -> Tensor:
+    """nn.MaxPool2d(2) on (N, C, H, W) (frvsr_net.py:127); odd sizes floor."""
+    if x.dim() != 4:
+        raise ValueError(f"vsrk::max_pool2x2 expects (N, C, H, W), got {tuple(x.shape)}")
+    xv = _to_cl(x, x.dtype)
+    n, d, h, w, c = xv.shape
+    yv = _empty_cl((n, d, h // 2, w // 2), c, x.dtype, x.device)
+    F.max_pool2x2(xv, yv)
+    return _from_cl(yv, True, x.dtype)
+
+
+@max_pool2x2.register_fake
+def _(x):
+    n, c, h, w = x.shape
+    return x.new_empty((n, c, h // 2, w // 2))
+
+
+@torch.library.custom_op("vsrk::max_pool2x2_backward", mutates_args=())
+def max_pool2x2_backward(grad: Tensor, x: Tensor) -> Tensor:
+    """grad_x of vsrk::max_pool2x2: grad routed to each window's first maximum."""
+    xv, gv = _to_cl(x, x.dtype), _to_cl(grad, x.dtype)
+    dxv = _empty_cl(xv.shape[:-1], xv.shape[-1], x.dtype, x.device)
+    F.max_pool2x2_bwd(xv, gv, dxv)
+    return _from_cl(dxv, True, x.dtype)
+
+
+@max_pool2x2_backward.register_fake
+def _(grad, x):
+    return x.new_empty(x.shape)
+
+
+def _pool_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0])
+
+
+def _pool_bwd(ctx, grad):
+    return max_pool2x2_backward(grad.contiguous(), ctx.saved_tensors[0])
+
+
+max_pool2x2.register_autograd(_pool_bwd, setup_context=_pool_setup)
 
 
 # ----------------------------------------------------------- DUF filter --

@@ -32,8 +32,10 @@ SISR, SISR-SRFB, MISR and VSR subclasses.  What changes, and why:
     NameError whenever that scheduler is used); it is stepped here with the
     validation loss, which is what the branch evidently intends.
 
-The FRVSR trainers (acdc/dsb15_frvsr_trainer.py) belong to a generator this
-build does not provide and are not mirrored.
+The FRVSR trainers (acdc/dsb15_frvsr_trainer.py) override _run_epoch in the
+reference only to hand the inputs to _compute_losses and to log outputs[0];
+here BaseTrainer._run_epoch has two small hooks for that (_losses,
+_logged_outputs), so they share the step above.
 """
 from __future__ import annotations
 
@@ -147,7 +149,7 @@ class BaseTrainer:
             inputs, targets = self._get_inputs_targets(batch)
             if mode == 'training':
                 outputs = self.net(inputs)
-                losses = self._compute_losses(outputs, targets)
+                losses = self._losses(outputs, inputs, targets)
                 loss = (torch.stack(losses) * self.loss_weights).sum()
                 self.optimizer.zero_grad()
                 loss.backward()
@@ -159,7 +161,7 @@ class BaseTrainer:
             else:
                 with torch.no_grad():
                     outputs = self.net(inputs)
-                    losses = self._compute_losses(outputs, targets)
+                    losses = self._losses(outputs, inputs, targets)
                     loss = (torch.stack(losses) * self.loss_weights).sum()
             with torch.no_grad():
                 metrics = self._compute_metrics(outputs, targets)
@@ -167,7 +169,15 @@ class BaseTrainer:
             T = self._frames(inputs)
             self._update_log(log, batch_size * T, loss, losses, metrics)
             count += batch_size * T
-        return self._finish_log(log, count), batch, outputs
+        return self._finish_log(log, count), batch, self._logged_outputs(outputs)
+
+    def _losses(self, outputs, inputs, targets):
+        """The step's losses; trainers whose losses also read the inputs (FRVSR) override this."""
+        return self._compute_losses(outputs, targets)
+
+    def _logged_outputs(self, outputs):
+        """What _run_epoch hands to the logger (FRVSR: the SR frames of its output pair)."""
+        return outputs
 
     def _finish_log(self, log, count):
         keys = list(log)
@@ -331,4 +341,42 @@ class AcdcVSRTrainer(BaseTrainer):
 
 
 class Dsb15VSRTrainer(AcdcVSRTrainer):
+    dataset = "dsb15"
+
+
+# --------------------------------------------------------------- FRVSR --
+class AcdcFRVSRTrainer(BaseTrainer):
+    """acdc_frvsr_trainer.py:9-126.  The net returns (sr_imgs, lr_imgs): the
+    first loss function compares each warped previous frame with its frame,
+    the second each estimate with its target (two nn.L1Loss entries add into
+    the one 'L1Loss' log key, as in the reference); metrics and the logger
+    see the SR frames; logs are weighted by batch_size * T."""
+
+    dataset = "acdc"
+
+    def _frames(self, inputs) -> int:
+        return len(inputs)
+
+    def _get_inputs_targets(self, batch):
+        return batch['lr_imgs'], batch['hr_imgs']
+
+    def _losses(self, outputs, inputs, targets):
+        return self._compute_losses(outputs, inputs, targets)
+
+    def _compute_losses(self, outputs, lr_imgs, hr_imgs):
+        sr_imgs, lr_imgs_ = outputs
+        flow_loss = torch.stack([self.loss_fns[0](a, b) for a, b in zip(lr_imgs_, lr_imgs)]).mean()
+        sr_loss = torch.stack([self.loss_fns[1](a, b) for a, b in zip(sr_imgs, hr_imgs)]).mean()
+        return [flow_loss, sr_loss]
+
+    def _compute_metrics(self, outputs, targets):
+        sr_imgs, _ = outputs
+        return [torch.stack([_metric(fn, o, t, self.dataset) for o, t in zip(sr_imgs, targets)]).mean()
+                for fn in self.metric_fns]
+
+    def _logged_outputs(self, outputs):
+        return outputs[0] if outputs is not None else None
+
+
+class Dsb15FRVSRTrainer(AcdcFRVSRTrainer):
     dataset = "dsb15"
