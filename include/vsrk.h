@@ -156,26 +156,44 @@ int vsrk_conv_fwd_prelu_bwd(const vsrk_conv_desc* desc, const vsrk_tensor5* x, c
                             const float* bias, const vsrk_tensor5* y_fwd, const vsrk_tensor5* y, int32_t c_lo,
                             float* da, int32_t accumulate_da, void* workspace, size_t workspace_bytes, void* stream);
 
-/* Tuning knob for A/B measurement: -1 (default) = bf16 fast path when
- * eligible (env VSRK_CONV_FAST=0 disables), 0 = always the generic kernel,
- * 1 = fast path when eligible.  Results agree within bf16 rounding. */
+/* Tuning knob for A/B measurement, an alias of path "fast" of
+ * vsrk_conv_set_path: 0 = always the generic kernel, 1 = the bf16 fast path
+ * when eligible, -1 = the value at load (on unless VSRK_CONV_FAST=0).  Results
+ * agree within bf16 rounding. */
 int vsrk_conv_set_algo(int32_t mode);
 
-/* Per-path switch for A/B measurement and tests: path "fast" (bf16 LDS-DMA
- * conv, default on), "pw"
- * (bf16 1x1x1 convs with cin = cout or cout a multiple of cin, cin <= 256:
- * forward, data gradient and weight gradient in one pass over HBM, default
- * on), "thin" (cin <= 4 / cout <= 3 kernels incl. their weight gradient,
- * default on), "wgrad_pipe" (pipelined 16-bit 3x3(x3) weight gradient, default
- * on), "wgrad_roll" (rolling-depth Conv3d 3x3x3 weight gradient), "wgrad_row"
- * (rolling-row Conv2d 3x3 weight gradient over 64 x 64 channel blocks,
- * default on), "roll_fold" (the depth-folded rolling forward of a Conv3d
- * 3x3x3 with one output depth from three slices, duf_net.py:214, default on;
- * env VSRK_ROLL_FOLD); mode -1 = default/environment (VSRK_CONV_FAST, VSRK_CONV_PW,
- * VSRK_CONV_ROLL, VSRK_CONV_THIN, VSRK_WGRAD_PIPE, VSRK_WGRAD_ROLL,
- * VSRK_WGRAD_ROW), 0 = off, 1 = on where eligible.  Every path computes the
- * same result as the generic kernels within bf16 rounding. */
+/* Per-path switches for A/B measurement and tests, one per kernel family.
+ * Each is read once from its environment variable when the library is loaded
+ * (a value starting with '0' = 0, any other value = 1, unset = the default
+ * below); set_path changes it: 0 = off, 1 = on where eligible, 2 where
+ * noted, -1 = back to the value at load.  get_path returns the effective mode.
+ *
+ *   path        variable           unset  family
+ *   fast        VSRK_CONV_FAST     1      bf16 LDS-DMA conv
+ *   pw          VSRK_CONV_PW       1      16-bit 1x1x1 convs with cin = cout or cout a multiple of cin,
+ *                                         cin <= 256: forward, data and weight gradient in one pass over HBM
+ *   pw_wide     VSRK_PW_WIDE       1      1x1x1 convs with > 256 input channels or 256 -> >= 256
+ *   roll        VSRK_CONV_ROLL     2      rolling-depth Conv3d 3x3x3 and its 2-D 3x3 forms; 1 = every eligible
+ *                                         shape, 2 (not settable) = also skip shallow output depths where it is slower
+ *   roll_wr     VSRK_ROLL_WRES     1      the rolling conv's resident weights; 2 = also with the prefetched
+ *                                         residual / mask epilogue (slower); 0 or 2 keep the row kernel aside
+ *   roll_fold   VSRK_ROLL_FOLD     1      depth-folded rolling forward of a Conv3d 3x3x3 with one output depth
+ *                                         from three slices (duf_net.py:214)
+ *   row         VSRK_CONV_ROW      -1     row-walking 3x3 64 -> 64 conv, reached through roll; -1 = the epilogue
+ *                                         forms that measured faster than the tile kernel, 1 = every form
+ *   thin        VSRK_CONV_THIN     1      cin <= 4 / cout <= 3 kernels incl. their weight gradient
+ *   stencil     VSRK_CONV_STENCIL  1      one-input / one-output channel 3x3 stencils, reached through thin
+ *   wgrad_pipe  VSRK_WGRAD_PIPE    1      pipelined 16-bit 3x3(x3) weight gradient
+ *   wgrad_roll  VSRK_WGRAD_ROLL    2      rolling-depth Conv3d 3x3x3 weight gradient; modes as roll
+ *   wgrad_row   VSRK_WGRAD_ROW     1      rolling-row Conv2d 3x3 weight gradient over 64 x 64 channel blocks;
+ *                                         2 = also the sub-pixel tap-skip views
+ *
+ * Every path computes the same result as the generic kernels within bf16
+ * rounding.  The modes are process-wide test / A-B switches: set them between
+ * launches, never concurrently with launches on another thread; otherwise
+ * they are constant after load. */
 int vsrk_conv_set_path(const char* path, int32_t mode);
+int vsrk_conv_get_path(const char* path, int32_t* mode);
 
 /* Test knob: cap the persistent conv grids (forward / data-gradient kernels)
  * and the weight-gradient split at max_workgroups (0 = default: one

@@ -521,8 +521,9 @@ FOLD_CASES = [
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("case", FOLD_CASES)
 def test_roll_depth_fold(case, dtype):
-    """the depth-folded form (conv_roll_fold.hip: 3 slices -> 1 output depth
-    as a 3x3 conv over (kd, channel) chunks, 32-row tiles) against fp64 with
+    """the depth-folded form (conv_roll_fold.hip, conv_roll_impl.h's kernel
+    built with 32-row tiles: 3 slices -> 1 output depth as a 3x3 conv over
+    (kd, channel) chunks) against fp64 with
     and without the BN prologue, bitwise invariant under the grid cap, and
     bitwise equal to the 3-D rolling form it replaces (both accumulate an
     output voxel slice by slice, chunk by chunk, tap by tap)"""

@@ -304,8 +304,6 @@ bool vsrk_wgrad_roll_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, const 
 int vsrk_conv_wgrad_roll(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy,
                          const float* pro_scale, const float* pro_shift, int want_bias, float* ws, size_t ws_bytes,
                          int* nsplit_out, hipStream_t s);
-void vsrk_conv_set_wgrad_roll_mode(int mode);
-extern int vsrk_g_roll_dz;  // vsrk_conv_set_roll_depth (conv_roll.hip)
 // rolling-row 16-bit Conv2d 3x3 weight gradient (conv_wgrad_row.hip): plan
 // (false = not eligible) and launch (1 = launched the slab kernel, whose slabs
 // wgrad_reduce_kernel sums over nsplit splits and ncot * ncic combos of
@@ -318,7 +316,6 @@ struct VsrkRowPlan {
 bool vsrk_wgrad_row_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy, VsrkRowPlan* p);
 int vsrk_conv_wgrad_row(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy, int want_bias,
                         float* ws, size_t ws_bytes, VsrkRowPlan* plan, hipStream_t s);
-void vsrk_conv_set_wgrad_row_mode(int mode);
 // thin-channel weight gradient (conv_thin.hip): 1 = launched the slab kernel, 0 = not eligible.
 int vsrk_conv_wgrad_thin(const vsrk_conv::WgradArgs& a, int nco, int nci, int perm_r, int dtype, hipStream_t s);
 

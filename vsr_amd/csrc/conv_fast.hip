@@ -2,69 +2,16 @@
 // and data-gradient): eligibility, argument set-up and dispatch to the tile
 // families instantiated in conv_fast_*.hip.  The kernel and its design notes
 // are in conv_fast_impl.h.
-#include <cstdlib>
-#include <string>
 #include "conv_fast_impl.h"
 
-namespace {
 using namespace vsrk_conv;
 
-int g_fast_mode = -1;  // -1: from VSRK_CONV_FAST (default on), 0 off, 1 on
-
-int num_cus_fast() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
-}  // namespace
-
-int vsrk_g_grid_cap = 0;  // vsrk_conv_set_grid_cap: 0 = one workgroup per CU
+static const int g_fast_ablate = vsrk_env_int("VSRK_FAST_ABLATE", 0);  // diagnostics only (FastArgs::ablate)
 
 int vsrk_conv::fast_grid(int64_t ntiles) {
-  int64_t g = std::min<int64_t>(ntiles, (int64_t)num_cus_fast());
+  int64_t g = std::min<int64_t>(ntiles, (int64_t)vsrk_num_cus());
   if (vsrk_g_grid_cap > 0) g = std::min<int64_t>(g, vsrk_g_grid_cap);
   return (int)std::max<int64_t>(g, 1);
-}
-
-extern "C" int vsrk_conv_set_algo(int32_t mode) {
-  VSRK_CHECK(mode >= -1 && mode <= 1, "conv_set_algo: mode must be -1, 0 or 1");
-  g_fast_mode = mode;
-  return VSRK_OK;
-}
-
-extern int g_pw_wide_mode;  // conv_pw_wide.hip
-
-extern "C" int vsrk_conv_set_path(const char* path, int32_t mode) {
-  VSRK_CHECK(path, "conv_set_path: null path");
-  const std::string p(path);
-  VSRK_CHECK(mode >= -1 && mode <= (p == "wgrad_row" || p == "roll_wr" ? 2 : 1),
-             "conv_set_path: mode must be -1, 0 or 1 (wgrad_row, roll_wr: 2)");
-  if (p == "fast") g_fast_mode = mode;
-  else if (p == "thin") vsrk_g_thin_mode = mode;
-  else if (p == "wgrad_pipe") vsrk_g_wgrad_pipe_mode = mode;
-  else if (p == "pw") vsrk_g_pw_mode = mode;
-  else if (p == "roll") vsrk_conv_set_roll_mode(mode);
-  else if (p == "wgrad_roll") vsrk_conv_set_wgrad_roll_mode(mode);
-  else if (p == "wgrad_row") vsrk_conv_set_wgrad_row_mode(mode);
-  else if (p == "roll_wr") vsrk_conv_set_roll_wr_mode(mode);
-  else if (p == "roll_fold") vsrk_conv_set_roll_fold_mode(mode);
-  else if (p == "stencil") vsrk_conv_set_stencil_mode(mode);
-  else if (p == "pw_wide") g_pw_wide_mode = mode;
-  else if (p == "row") vsrk_conv_set_row_mode(mode);
-  else VSRK_CHECK(false, "conv_set_path: unknown path '%s' (fast, pw, pw_wide, roll, roll_wr, roll_fold, row, thin, wgrad_pipe, wgrad_roll, wgrad_row, stencil)",
-                  path);
-  return VSRK_OK;
-}
-
-extern "C" int vsrk_conv_set_grid_cap(int32_t max_workgroups) {
-  VSRK_CHECK(max_workgroups >= 0, "conv_set_grid_cap: max_workgroups must be >= 0");
-  vsrk_g_grid_cap = max_workgroups;
-  return VSRK_OK;
 }
 
 // Returns 1 and launches when the fast path covers the request, 0 when the
@@ -72,11 +19,7 @@ extern "C" int vsrk_conv_set_grid_cap(int32_t max_workgroups) {
 int vsrk_conv_fwd_fast(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed, const float* bias,
                        const float* pro_scale, const float* pro_shift, const vsrk_tensor5* residual,
                        const vsrk_tensor5* mask, const vsrk_tensor5* y, hipStream_t s) {
-  if (g_fast_mode < 0) {
-    const char* e = getenv("VSRK_CONV_FAST");
-    g_fast_mode = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (g_fast_mode == 0) return 0;
+  if (vsrk_path_mode(VSRK_PATH_FAST) == 0) return 0;
   if (!vsrk_is16(x->dtype)) return 0;
   if (const int rl = vsrk_conv_fwd_roll(d, x, w_packed, bias, pro_scale, pro_shift, residual, mask, y, s)) return rl;
   if (!chunk_ok(x, 2) || x->c % 8 != 0) return 0;
@@ -95,12 +38,7 @@ int vsrk_conv_fwd_fast(const vsrk_conv_desc* d, const vsrk_tensor5* x, const voi
       return 0;
   }
   FastArgs a;
-  static int ablate = -1;
-  if (ablate < 0) {
-    const char* e = getenv("VSRK_FAST_ABLATE");
-    ablate = e ? atoi(e) : 0;
-  }
-  a.ablate = ablate;
+  a.ablate = g_fast_ablate;
   a.x = make_view(x);
   a.y = make_view(y);
   a.res = residual ? make_view(residual) : a.y;

@@ -446,15 +446,8 @@ extern "C" int vsrk_conv_pack_weights(int32_t dtype, int32_t n, const vsrk_pack_
   return VSRK_OK;
 }
 
-static int num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
+// VSRK_LOG_DISPATCH=1: one stderr line per launch -- the path taken and the shapes (diagnostics)
+static const bool g_log_dispatch = vsrk_env_int("VSRK_LOG_DISPATCH", 0) == 1;
 
 template <typename T, int NT, int KK, int XM, typename YT>
 static int launch_fwd(ConvArgs a, hipStream_t s) {
@@ -473,7 +466,7 @@ static int launch_fwd(ConvArgs a, hipStream_t s) {
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, NTHR, lds) != hipSuccess || per_cu < 1)
     per_cu = 1;
-  const int64_t grid = vsrk_capped_grid(std::min<int64_t>(ntiles, (int64_t)num_cus() * per_cu));
+  const int64_t grid = vsrk_capped_grid(std::min<int64_t>(ntiles, (int64_t)vsrk_num_cus() * per_cu));
   a.nblk = (int)grid;
   kern<<<a.nblk, NTHR, lds, s>>>(a);
   VSRK_LAUNCH_CHECK("conv_fwd");
@@ -561,14 +554,8 @@ extern "C" int vsrk_conv_fwd(const vsrk_conv_desc* d, const vsrk_tensor5* x, con
   const int NT = y->c <= 32 ? 32 : ((y->c <= 64 || d->kh == 3) ? 64 : 128);
   a.ntn = ceil_div(y->c, NT);
   hipStream_t s = (hipStream_t)stream;
-  // VSRK_LOG_DISPATCH=1: one stderr line per launch -- the path taken and the shapes (diagnostics)
-  static int log_dispatch = -1;
-  if (log_dispatch < 0) {
-    const char* e = getenv("VSRK_LOG_DISPATCH");
-    log_dispatch = (e && e[0] == '1') ? 1 : 0;
-  }
   auto logd = [&](const char* path) {
-    if (log_dispatch)
+    if (g_log_dispatch)
       fprintf(stderr, "vsrk_conv_fwd %s k=%dx%dx%d x=(%d,%d,%d,%d,%d) y=(%d,%d,%d,%d,%d)%s pro=%d act=%d mask=%d res=%d acc=%d\n",
               path, d->kd, d->kh, d->kw, x->n, x->d, x->h, x->w, x->c, y->n, y->d, y->h, y->w, y->c,
               ydt == VSRK_F32 ? " f32out" : "", d->prologue, d->act, mask != nullptr, residual != nullptr, d->accumulate);

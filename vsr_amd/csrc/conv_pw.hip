@@ -25,11 +25,8 @@
 //    one fp32 partial slab; pw_wgrad_reduce sums the slabs in split order
 //    (deterministic).  One pass over dY and X per cin/cout chunk.
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 #include "conv_common.h"
-
-int vsrk_g_pw_mode = -1;  // -1: from VSRK_CONV_PW (default on), 0 off, 1 on
 
 namespace {
 using namespace vsrk_conv;
@@ -47,23 +44,17 @@ constexpr int PW_KP = 64;    // wgrad voxels per stage
 #define PW_BXPRE 1  // fused BN-backward reduce: BN input rows loaded ahead of the MFMAs (0: in the store pass)
 #endif
 
-static bool pw_enabled() {
-  if (vsrk_g_pw_mode < 0) {
-    const char* e = getenv("VSRK_CONV_PW");
-    vsrk_g_pw_mode = (e && e[0] == '0') ? 0 : 1;
-  }
-  return vsrk_g_pw_mode == 1;
-}
-
-static int pw_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
+// A/B knobs, read at load
+const int g_pw_staged = vsrk_env_flag("VSRK_PW_STAGED", 1);    // 0: no staged (LDS row buffer) kernel
+const int g_pw_staged8 = vsrk_env_flag("VSRK_PW_STAGED8", 1);  // 0: 256 input channels on the tile kernel
+const int g_pw_ablate = vsrk_env_int("VSRK_PW_ABLATE", 0);     // diagnostics only (PwArgs::ablate)
+// weight gradient: input chunks of up to 8 blocks (1), of 4 (any other value), unset: automatic (-2)
+const int g_pw_wgrad_ci8 = [] {
+  const int v = vsrk_env_int("VSRK_PW_WGRAD_CI8", -2);
+  return v == -2 ? -2 : (v == 1 ? 1 : 0);
+}();
+const int g_pw_wgrad_nw8 = vsrk_env_flag("VSRK_PW_WGRAD_NW8", 1);  // the 8-wave form
+const int g_pw_wgrad_depth = vsrk_env_int("VSRK_PW_WGRAD_DEPTH", 2) == 1 ? 1 : 2;  // stages in flight
 
 // Division by a launch constant d (dividends < 2^31), branch-free:
 // q = (x * mul) >> p with p = 31 + ceil(log2 d), mul = ceil(2^p / d) < 2^32.
@@ -1207,12 +1198,7 @@ static bool dhw_dense(const vsrk_tensor5* t) {
 template <int NCB, int NKB, int M, typename H>
 static bool launch_fwd_staged(const PwArgs& a, int grid, int nchunk, bool pro, hipStream_t s) {
   constexpr int KS = 2 * NKB, COP = 32 * NCB, CIP = 16 * KS;
-  static int staged = -1;
-  if (staged < 0) {
-    const char* e = getenv("VSRK_PW_STAGED");
-    staged = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (!staged || a.cout % 8 != 0) return false;
+  if (!g_pw_staged || a.cout % 8 != 0) return false;
   const bool ein = a.has_mask || a.accumulate || a.pbwd;
   if (ein && (pro || a.act != VSRK_ACT_NONE)) return false;  // data gradients: no prologue / activation
   if (pro && a.act == VSRK_ACT_PRELU) return false;
@@ -1265,7 +1251,7 @@ static bool launch_fwd_staged(const PwArgs& a, int grid, int nchunk, bool pro, h
 }
 
 static int pw_grid(int64_t ntiles) {
-  int grid = (int)std::min<int64_t>(pw_num_cus(), ceil_div64(ntiles, PW_THR / 64));
+  int grid = (int)std::min<int64_t>(vsrk_num_cus(), ceil_div64(ntiles, PW_THR / 64));
   if (vsrk_g_grid_cap > 0) grid = std::min(grid, vsrk_g_grid_cap);
   return std::max(grid, 1);
 }
@@ -1282,12 +1268,7 @@ static bool launch_fwd(const PwArgs& a, int nchunk, bool pro, hipStream_t s) {
     // 256 input channels: the staged kernel in two 128-channel output chunks
     // per 256 (x read twice, once per chunk, at the staged kernel's rate; the
     // tile kernel below ran DUF's 256 -> 256 / 512 heads at 1.5-2 TB/s)
-    static int st8 = -1;  // A/B knob VSRK_PW_STAGED8=0
-    if (st8 < 0) {
-      const char* e = getenv("VSRK_PW_STAGED8");
-      st8 = (e && e[0] == '0') ? 0 : 1;
-    }
-    if (st8 && M == 1 && launch_fwd_staged<4, 8, 1, H>(a, grid, 2 * nchunk, pro, s)) return true;
+    if (g_pw_staged8 && M == 1 && launch_fwd_staged<4, 8, 1, H>(a, grid, 2 * nchunk, pro, s)) return true;
   }
   if (a.act == VSRK_ACT_PRELU) return false;
   const bool ein = a.has_mask || a.accumulate;
@@ -1336,12 +1317,7 @@ static bool pw_fill_args(PwArgs& a, const vsrk_conv_desc* d, const vsrk_tensor5*
       if (t && 2 * (span_n * t->sn + (int64_t)a.dhw * t->sw + t->c) >= 0x7FFFFFF0ll) return false;
     }
   }
-  static int ablate = -1;
-  if (ablate < 0) {
-    const char* e = getenv("VSRK_PW_ABLATE");
-    ablate = e ? atoi(e) : 0;
-  }
-  a.ablate = ablate;
+  a.ablate = g_pw_ablate;
   a.cin = x->c;
   a.cout = y->c;
   a.ci_pad = cip;
@@ -1387,12 +1363,12 @@ int vsrk_conv_fwd_pw_pbwd(const vsrk_conv_desc* d, const vsrk_tensor5* x, const 
 }
 
 // grid <= CUs, <= 2 output chunks, one partial per wave
-size_t vsrk_pw_pbwd_ws_bytes() { return (size_t)pw_num_cus() * 2 * (PW_THR / 64) * sizeof(double); }
+size_t vsrk_pw_pbwd_ws_bytes() { return (size_t)vsrk_num_cus() * 2 * (PW_THR / 64) * sizeof(double); }
 
 static int fwd_pw_impl(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed, const float* bias,
                        const float* pro_scale, const float* pro_shift, const vsrk_tensor5* residual,
                        const vsrk_tensor5* mask, const vsrk_tensor5* y, hipStream_t s, const PwPbwd* pb) {
-  if (!pw_enabled()) return 0;
+  if (!vsrk_path_mode(VSRK_PATH_PW)) return 0;
   if (!vsrk_is16(x->dtype) || y->dtype != x->dtype) return 0;
   if (d->kd != 1 || d->kh != 1 || d->kw != 1 || d->pd || d->ph || d->pw) return 0;
   if (residual || d->bias_perm_r > 1) return 0;
@@ -1512,9 +1488,20 @@ static int fwd_pw_impl(const vsrk_conv_desc* d, const vsrk_tensor5* x, const voi
 }
 
 extern "C" size_t vsrk_conv_fwd_reduce_workspace(const vsrk_conv_desc* d, const vsrk_tensor5* y) {
-  const size_t pw = (size_t)pw_num_cus() * (PW_THR / 64) * 64 * 16 * sizeof(float);
+  const size_t pw = (size_t)vsrk_num_cus() * (PW_THR / 64) * 64 * 16 * sizeof(float);
   if (d && y && d->kd == 3) return std::max(pw, vsrk_roll_bnred_ws_floats(y) * sizeof(float));
   return pw;
+}
+
+// the sums of a launch with nothing to reduce
+static int pw_zero_sums(float* out_a, float* out_b, int c, hipStream_t s) {
+  hipError_t e = hipMemsetAsync(out_a, 0, sizeof(float) * c, s);
+  if (e == hipSuccess) e = hipMemsetAsync(out_b, 0, sizeof(float) * c, s);
+  if (e != hipSuccess) {
+    vsrk_set_error("conv_fwd_reduce: clearing the sums failed: %s", hipGetErrorString(e));
+    return VSRK_ERR_LAUNCH;
+  }
+  return VSRK_OK;
 }
 
 // q (with qx, xo): the BNB input form (vsrk_conv_fwd_reduce_bnb), x = q->dz
@@ -1535,15 +1522,11 @@ static int fwd_reduce_impl(const vsrk_conv_desc* d, const vsrk_tensor5* x, const
     const int rc = vsrk_conv_fwd_roll(d, x, w_packed, bias, nullptr, nullptr, nullptr, nullptr, y, s, nullptr, &r);
     if (rc == 0) return VSRK_ERR_UNSUPPORTED;
     if (rc < 0) return -rc;
-    if (r.ntiles == 0) {
-      (void)hipMemsetAsync(out_a, 0, sizeof(float) * y->c, s);
-      (void)hipMemsetAsync(out_b, 0, sizeof(float) * y->c, s);
-      return VSRK_OK;
-    }
+    if (r.ntiles == 0) return pw_zero_sums(out_a, out_b, y->c, s);
     return vsrk_roll_bnred_final(r, y->c, out_a, out_b, s);
   }
   // eligible: a square pointwise conv on the staged kernel, no epilogue operands
-  if (!pw_enabled() || !vsrk_is16(x->dtype) || y->dtype != x->dtype) return VSRK_ERR_UNSUPPORTED;
+  if (!vsrk_path_mode(VSRK_PATH_PW) || !vsrk_is16(x->dtype) || y->dtype != x->dtype) return VSRK_ERR_UNSUPPORTED;
   if (d->kd != 1 || d->kh != 1 || d->kw != 1 || d->pd || d->ph || d->pw || d->bias_perm_r > 1) return VSRK_ERR_UNSUPPORTED;
   if (d->act != VSRK_ACT_NONE || d->accumulate || d->out_scale != 1.f) return VSRK_ERR_UNSUPPORTED;
   if ((mode == 1) != (d->prologue != VSRK_PRO_NONE)) return VSRK_ERR_UNSUPPORTED;
@@ -1600,18 +1583,14 @@ static int fwd_reduce_impl(const vsrk_conv_desc* d, const vsrk_tensor5* x, const
   VSRK_CHECK(workspace && workspace_bytes >= vsrk_conv_fwd_reduce_workspace(d, y),
              "conv_fwd_reduce: workspace %zu < %zu bytes", workspace_bytes, vsrk_conv_fwd_reduce_workspace(d, y));
   a.red_ws = (float*)workspace;
-  if (a.nvox == 0) {
-    (void)hipMemsetAsync(out_a, 0, sizeof(float) * y->c, s);
-    (void)hipMemsetAsync(out_b, 0, sizeof(float) * y->c, s);
-    return VSRK_OK;
-  }
+  if (a.nvox == 0) return pw_zero_sums(out_a, out_b, y->c, s);
   int grid = 0;
   vsrk_dispatch16(x->dtype, [&](auto tag) {
     using H = decltype(tag);
     auto go = [&](auto ncb_c) {
       constexpr int NC = decltype(ncb_c)::value;
       a.ntiles = ceil_div(a.nvox, 32 * pw_m<NC>());
-      grid = std::min(pw_grid(a.ntiles), pw_num_cus());
+      grid = std::min(pw_grid(a.ntiles), vsrk_num_cus());
       if (mode == 1) launch_fwd_reduce<NC, pw_m<NC>(), 1, H>(a, grid, s);
       else if (q) launch_fwd_reduce<NC, pw_m<NC>(), 2, H, true>(a, grid, s);
       else launch_fwd_reduce<NC, pw_m<NC>(), 2, H>(a, grid, s);
@@ -1663,7 +1642,7 @@ struct PwWPlan {
 PwWPlan pw_wgrad_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy) {
   PwWPlan p{};
   p.ok = false;
-  if (!pw_enabled()) return p;
+  if (!vsrk_path_mode(VSRK_PATH_PW)) return p;
   if (!vsrk_is16(x->dtype) || dy->dtype != x->dtype) return p;
   if (d->kd != 1 || d->kh != 1 || d->kw != 1 || d->pd || d->ph || d->pw) return p;
   if (x->n != dy->n || x->d != dy->d || x->h != dy->h || x->w != dy->w) return p;
@@ -1683,18 +1662,9 @@ PwWPlan pw_wgrad_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk
   // unit 5 (224 -> 224) 1568 -> 1071 us, the heads 256 -> 512 / 512 -> 400 /
   // 256 -> 256 910 / 1741 / 479 -> 657 / 1169 / 372 us; at 160 and 192
   // channels the split runs two workgroups per CU and stays ahead.
-  static int ci8 = -1;
-  if (ci8 == -1) {
-    const char* e = getenv("VSRK_PW_WGRAD_CI8");
-    ci8 = !e ? -2 : (e[0] == '1' ? 1 : 0);  // -2: automatic
-  }
   // 8-wave form (VSRK_PW_WGRAD_NW8, default on): chunks of up to 8 X blocks,
   // one per wave, wherever the input has more than 4 blocks
-  static int nw8 = -1;
-  if (nw8 == -1) {
-    const char* e = getenv("VSRK_PW_WGRAD_NW8");
-    nw8 = !(e && e[0] == '0');
-  }
+  const int ci8 = g_pw_wgrad_ci8, nw8 = g_pw_wgrad_nw8;
   p.nw = (nw8 && cib > 4 && ci8 != 0) ? 8 : 4;
   const bool one_chunk = p.nw == 8 || ci8 == 1 || (ci8 == -2 && cib > 4 && std::min(cob, 8) + 4 > 10);
   p.ncit = std::min(cib, one_chunk ? 8 : 4);
@@ -1714,7 +1684,7 @@ PwWPlan pw_wgrad_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk
   const int64_t steps = std::max<int64_t>(1, ceil_div64(nvox, PW_KP));
   // two workgroups per CU where the double-buffered stage fits LDS twice
   const size_t lds = (size_t)2 * (p.nco + p.nw * p.ncoiw) * PW_KP * 64;
-  int want = std::max(1, pw_num_cus() * (lds <= 80 * 1024 ? 2 : 1) / p.nchunks);
+  int want = std::max(1, vsrk_num_cus() * (lds <= 80 * 1024 ? 2 : 1) / p.nchunks);
   if (vsrk_g_grid_cap > 0) want = std::max(1, vsrk_g_grid_cap / p.nchunks);
   want = (int)std::min<int64_t>(want, steps);
   p.vps = ceil_div64(steps, want) * PW_KP;
@@ -1725,20 +1695,10 @@ PwWPlan pw_wgrad_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk
   return p;
 }
 
-// stages in flight (VSRK_PW_WGRAD_DEPTH=1|2, default 2)
-int pw_wgrad_depth() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("VSRK_PW_WGRAD_DEPTH");
-    v = (e && e[0] == '1') ? 1 : 2;
-  }
-  return v;
-}
-
 template <int NCO, int NCIW, typename H, int NW = 4>
 void launch_wgrad_pw(const PwWArgs& a, int nsplit, hipStream_t s) {
   const size_t lds = (size_t)2 * (NCO + NW * NCIW) * PW_KP * 64;
-  auto kern = pw_wgrad_depth() == 2 ? pw_wgrad_kernel<NCO, NCIW, H, 2, NW> : pw_wgrad_kernel<NCO, NCIW, H, 1, NW>;
+  auto kern = g_pw_wgrad_depth == 2 ? pw_wgrad_kernel<NCO, NCIW, H, 2, NW> : pw_wgrad_kernel<NCO, NCIW, H, 1, NW>;
   (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   kern<<<dim3(nsplit, a.nchunks), NW * 64, lds, s>>>(a);
 }

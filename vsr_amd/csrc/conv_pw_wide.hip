@@ -266,18 +266,12 @@ int64_t voxel_stride(const vsrk_tensor5* t) {
 
 }  // namespace
 
-int g_pw_wide_mode = -1;  // -1: from VSRK_PW_WIDE (default on), 0 off
-
 // 1 = launched, 0 = not eligible (the caller goes on to the other kernels),
 // < 0 = -(error status)
 int vsrk_conv_fwd_pw_wide(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed, const float* bias,
                           const vsrk_tensor5* residual, const vsrk_tensor5* mask, const vsrk_tensor5* y,
                           hipStream_t s) {
-  if (g_pw_wide_mode < 0) {
-    const char* e = getenv("VSRK_PW_WIDE");
-    g_pw_wide_mode = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (!g_pw_wide_mode) return 0;
+  if (vsrk_path_mode(VSRK_PATH_PW_WIDE) == 0) return 0;
   if (d->kd != 1 || d->kh != 1 || d->kw != 1 || d->pd || d->ph || d->pw) return 0;
   if (!vsrk_is16(x->dtype) || !(y->dtype == x->dtype || y->dtype == VSRK_F32)) return 0;
   // the wide shapes only: more than 256 input channels, or 256 -> >= 256

@@ -64,7 +64,6 @@
 //    conv_roll's epilogue_sw): every global access is 16 contiguous bytes.
 //    The operand rows (residual, mask, old output for accumulate) are loaded
 //    into registers one stage ahead.  Rounds once, at the store.
-#include <cstdlib>
 #include "conv_common.h"
 
 namespace {
@@ -363,24 +362,6 @@ __global__ __launch_bounds__(CR_NW * 64, 1) void conv_row_kernel(ConvRowArgs a) 
 
 unsigned long long g_row_launches = 0;
 
-// -1: per-form default routing, 0 off, 1 every eligible form
-int cr_env_mode() {
-  const char* e = getenv("VSRK_CONV_ROW");
-  return !e ? -1 : (e[0] == '0' ? 0 : 1);
-}
-const int g_row_env = cr_env_mode();  // read once, when the library is loaded
-int g_row_mode = g_row_env;
-
-int cr_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
 template <int EM, typename H>
 int launch_row(const ConvRowArgs& a, int grid, hipStream_t s) {
   // (one segment: the form without the halo-column loads)
@@ -403,15 +384,14 @@ constexpr bool cr_default_on(int em) {
 // launches of the row kernel so far (tests: the routing, which the outputs do not show)
 extern "C" unsigned long long vsrk_conv_row_launches(void) { return g_row_launches; }
 
-void vsrk_conv_set_row_mode(int mode) { g_row_mode = mode < 0 ? g_row_env : mode; }
-
 // The caller (roll_fwd_one's 2-D branch) has checked: 16-bit x and y of one
 // type, 3x3, kd = 1, plain views, geometry of y / residual / mask, 8-byte
 // alignment of the output-shaped views, non-negative strides.
 // 1 = launched, 0 = not eligible, < 0 = -(error status)
 int vsrk_conv_fwd_row(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed, const float* bias,
                       const vsrk_tensor5* residual, const vsrk_tensor5* mask, const vsrk_tensor5* y, hipStream_t s) {
-  if (g_row_mode == 0) return 0;
+  const int mode = vsrk_path_mode(VSRK_PATH_ROW);  // -1: per-form default routing, 0 off, 1 every eligible form
+  if (mode == 0) return 0;
   if (d->kd != 1 || d->kh != 3 || d->kw != 3 || d->pd != 0 || d->ph != 1 || d->pw != 1) return 0;
   if (x->c != 64 || y->c != 64 || x->shuffle > 1 || y->shuffle > 1) return 0;
   if (d->prologue || d->mask_slope || d->bias_perm_r > 1 || d->subpixel) return 0;
@@ -420,7 +400,7 @@ int vsrk_conv_fwd_row(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void
   const int em = (residual ? CE_RES : 0) | (mask ? CE_MASK : 0) | (d->accumulate ? CE_ACC : 0) |
                  (d->act == VSRK_ACT_RELU ? CE_RELU : 0);
   if (em != 0 && em != CE_RELU && em != CE_RES && em != CE_MASK && em != (CE_RES | CE_ACC)) return 0;
-  if (g_row_mode < 0 && !cr_default_on(em)) return 0;
+  if (mode < 0 && !cr_default_on(em)) return 0;
   if (!chunk_ok(x, 2)) return 0;
   for (const vsrk_tensor5* t : {x, y, residual, mask}) {
     if (!t) continue;
@@ -450,7 +430,7 @@ int vsrk_conv_fwd_row(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void
   a.D = y->d; a.H = y->h; a.W = y->w;
   a.nseg = ceil_div(y->w, CR_SEG);
   // bands: as many as it takes for the (capped) grid to cover the CUs
-  const int64_t target = vsrk_capped_grid(cr_num_cus());
+  const int64_t target = vsrk_capped_grid(vsrk_num_cus());
   const int64_t cols = nimg * a.nseg;
   int64_t nb = std::max<int64_t>(1, std::min<int64_t>(ceil_div64(target, cols), y->h));
   a.band_h = (int)std::max<int64_t>(ceil_div64(y->h, nb), std::min(CR_MINBAND, y->h));
@@ -458,7 +438,7 @@ int vsrk_conv_fwd_row(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void
   const int64_t nitems = cols * a.nband;
   if (nitems >= (1ll << 31)) return 0;
   a.nitems = (int)nitems;
-  const int grid = (int)vsrk_capped_grid(std::min<int64_t>(nitems, cr_num_cus()));
+  const int grid = (int)vsrk_capped_grid(std::min<int64_t>(nitems, vsrk_num_cus()));
   int rc = vsrk_dispatch16(x->dtype, [&](auto tag) {
     using H = decltype(tag);
     switch (em) {

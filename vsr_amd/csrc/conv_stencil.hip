@@ -16,7 +16,6 @@
 // (1 KB contiguous).  The implicit-GEMM thin-input kernel (conv_thin.hip)
 // it replaces for these shapes ran the tail data gradient at 2.1 TB/s.
 #include <algorithm>
-#include <cstdlib>
 #include "conv_common.h"
 #include "vsrk_internal.h"
 
@@ -282,31 +281,16 @@ __global__ __launch_bounds__(256) void stencil_out_kernel(SoArgs a) {
   }
 }
 
-int g_stencil_mode = -1;  // -1: VSRK_CONV_STENCIL (unset: on), 0 off, 1 on
-
-int st_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
+// workgroups per CU of the one-input-channel form (VSRK_STENCIL_WG A/B: 2 / 4 / 8 / 16 -> 625 / 607 / 587 / 572 us)
+const int g_stencil_wg = std::max(1, vsrk_env_int("VSRK_STENCIL_WG", 16));
 
 }  // namespace
-
-void vsrk_conv_set_stencil_mode(int mode) { g_stencil_mode = mode; }
 
 // 1 = launched, 0 = not eligible (the thin / implicit-GEMM kernels run), < 0 = -(error status).
 int vsrk_conv_fwd_stencil(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed, const float* bias,
                           const vsrk_tensor5* residual, const vsrk_tensor5* mask, const vsrk_tensor5* y,
                           hipStream_t s) {
-  if (g_stencil_mode < 0) {
-    const char* e = getenv("VSRK_CONV_STENCIL");
-    g_stencil_mode = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (g_stencil_mode == 0) return 0;
+  if (vsrk_path_mode(VSRK_PATH_STENCIL) == 0) return 0;
   if (!vsrk_is16(x->dtype) || y->dtype != x->dtype) return 0;
   if (d->kd != 1 || d->kh != 3 || d->kw != 3 || d->pd != 0 || d->ph != 1 || d->pw != 1) return 0;
   if (d->prologue != VSRK_PRO_NONE || (d->act != VSRK_ACT_NONE && d->act != VSRK_ACT_RELU)) return 0;
@@ -335,19 +319,14 @@ int vsrk_conv_fwd_stencil(const vsrk_conv_desc* d, const vsrk_tensor5* x, const 
   a.ntiles = (int)ntiles;
   a.out_scale = d->out_scale;
   a.relu = d->act == VSRK_ACT_RELU;
-  static int per_cu = -1;  // workgroups per CU (VSRK_STENCIL_WG A/B: 2 / 4 / 8 / 16 -> 625 / 607 / 587 / 572 us)
-  if (per_cu < 0) {
-    const char* e = getenv("VSRK_STENCIL_WG");
-    per_cu = e ? std::max(1, atoi(e)) : 16;
-  }
-  const int want = (int)vsrk_capped_grid((int64_t)st_num_cus() * per_cu);
+  const int want = (int)vsrk_capped_grid((int64_t)vsrk_num_cus() * g_stencil_wg);
   a.tiles_per_blk = (int)ceil_div64(ntiles, want);
   // small launches (DRF's 1 -> 64 data gradient at 4 x 512^2: 2048 tiles) at
   // one tile per workgroup spend it on the per-workgroup setup (each lane's
   // 72 weights, the first patch): at least 4 tiles while the grid still
   // covers every CU
   if (vsrk_g_grid_cap <= 0)
-    a.tiles_per_blk = std::max(a.tiles_per_blk, (int)std::min<int64_t>(4, std::max<int64_t>(1, ntiles / st_num_cus())));
+    a.tiles_per_blk = std::max(a.tiles_per_blk, (int)std::min<int64_t>(4, std::max<int64_t>(1, ntiles / vsrk_num_cus())));
   const int grid = (int)ceil_div64(ntiles, a.tiles_per_blk);
   vsrk_dispatch16(x->dtype, [&](auto tag) {
     using H = decltype(tag);
@@ -366,11 +345,7 @@ int vsrk_conv_fwd_stencil(const vsrk_conv_desc* d, const vsrk_tensor5* x, const 
 int vsrk_conv_fwd_stencil_out(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed,
                               const float* bias, const vsrk_tensor5* residual, const vsrk_tensor5* mask,
                               const vsrk_tensor5* y, hipStream_t s) {
-  if (g_stencil_mode < 0) {
-    const char* e = getenv("VSRK_CONV_STENCIL");
-    g_stencil_mode = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (g_stencil_mode == 0) return 0;
+  if (vsrk_path_mode(VSRK_PATH_STENCIL) == 0) return 0;
   if (!vsrk_is16(x->dtype) || (y->dtype != x->dtype && y->dtype != VSRK_F32)) return 0;
   if (d->kd != 1 || d->kh != 3 || d->kw != 3 || d->pd != 0 || d->ph != 1 || d->pw != 1) return 0;
   if (d->prologue != VSRK_PRO_NONE || d->act != VSRK_ACT_NONE) return 0;
@@ -382,7 +357,7 @@ int vsrk_conv_fwd_stencil_out(const vsrk_conv_desc* d, const vsrk_tensor5* x, co
   const int nseg = ceil_div(y->w, SO_SEG);
   if (images * nseg == 0 || y->h == 0) return 1;
   // about 4 workgroups per CU; bands of >= 16 rows
-  const int64_t want = vsrk_capped_grid((int64_t)st_num_cus() * 4);
+  const int64_t want = vsrk_capped_grid((int64_t)vsrk_num_cus() * 4);
   int bands = (int)std::max<int64_t>(1, std::min<int64_t>(want / (images * nseg), ceil_div(y->h, 16)));
   SoArgs a;
   a.band_h = ceil_div(y->h, bands);

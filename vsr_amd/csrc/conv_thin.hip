@@ -617,23 +617,13 @@ __global__ __launch_bounds__(THR) __attribute__((amdgpu_waves_per_eu(NCI == 1 ? 
   }
 }
 
-int num_cus_thin() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
 template <typename KF>
 void launch_persistent(KF kern, ThinArgs& a, size_t lds, hipStream_t s) {
   (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, THR, lds) != hipSuccess || per_cu < 1)
     per_cu = 1;
-  const int want = (int)vsrk_capped_grid(num_cus_thin() * per_cu);
+  const int want = (int)vsrk_capped_grid(vsrk_num_cus() * per_cu);
   a.tiles_per_blk = ceil_div(a.ntiles, want);
   const int grid = ceil_div(a.ntiles, a.tiles_per_blk);
   kern<<<grid, THR, lds, s>>>(a);
@@ -641,22 +631,11 @@ void launch_persistent(KF kern, ThinArgs& a, size_t lds, hipStream_t s) {
 
 }  // namespace
 
-int vsrk_g_thin_mode = -1;  // -1: from VSRK_CONV_THIN (default on), 0 off, 1 on (vsrk_conv_set_path)
-
-static bool thin_enabled() {
-  int m = vsrk_g_thin_mode;
-  if (m < 0) {
-    const char* e = getenv("VSRK_CONV_THIN");
-    m = (e && e[0] == '0') ? 0 : 1;
-  }
-  return m != 0;
-}
-
 // 1 = launched; 0 = not a thin conv (the implicit-GEMM kernels run); < 0 = -(error status).
 int vsrk_conv_fwd_thin(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed, const float* bias,
                        const float* pro_scale, const float* pro_shift, const vsrk_tensor5* residual,
                        const vsrk_tensor5* mask, const vsrk_tensor5* y, hipStream_t s) {
-  if (!thin_enabled()) return 0;
+  if (vsrk_path_mode(VSRK_PATH_THIN) == 0) return 0;
   if (!vsrk_is16(x->dtype)) return 0;
   if (const int st = vsrk_conv_fwd_stencil(d, x, w_packed, bias, residual, mask, y, s)) return st;
   if (const int st = vsrk_conv_fwd_stencil_out(d, x, w_packed, bias, residual, mask, y, s)) return st;
@@ -751,7 +730,7 @@ int vsrk_conv_fwd_thin(const vsrk_conv_desc* d, const vsrk_tensor5* x, const voi
 // Weight gradient of a conv with cout <= 3 (the tail conv F -> 1): same plan
 // (splits x combos, slab size) as vsrk_conv_wgrad, so the reduce is shared.
 int vsrk_conv_wgrad_thin(const vsrk_conv::WgradArgs& a, int nco, int nci, int perm_r, int dtype, hipStream_t s) {
-  if (!thin_enabled()) return 0;
+  if (vsrk_path_mode(VSRK_PATH_THIN) == 0) return 0;
   if (nco != 1 || a.cout > 3 || a.kd != 1 || a.pd != 0 || a.kh != a.kw || a.kh * a.kw * a.cout > 32) return 0;
   if (a.cin % 8 || !a.xvec || a.x.r > 1 || a.dy.r > 1 || perm_r > 1) return 0;
   if (a.x.h != a.dy.h || a.x.w != a.dy.w || a.x.d != a.dy.d) return 0;

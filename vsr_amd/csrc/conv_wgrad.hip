@@ -1,6 +1,5 @@
 // Implicit-GEMM convolution weight/bias gradient on CDNA4 MFMA (gfx950).
 // Design notes: conv_fwd.hip (layout) and the comment block below.
-#include <cstdlib>
 #include "conv_common.h"
 
 namespace {
@@ -403,19 +402,20 @@ __global__ __launch_bounds__(256) void wgrad_reduce_rows_kernel(
   }
 }
 
+// A/B knobs, read at load
+const int g_wgrad_reduce = vsrk_env_flag("VSRK_WGRAD_REDUCE", 1);  // 0 keeps the per-output reduce kernel
+// VSRK_WGRAD_TARGET=<workgroups> (at least 64) overrides wgrad_plan's split rule; unset or 0: the rule
+const int g_wgrad_target_env = vsrk_env_int("VSRK_WGRAD_TARGET", 0);
+const int g_wgrad_target = g_wgrad_target_env ? std::max(64, g_wgrad_target_env) : 0;
+
 // the row-order reduce where it fits; VSRK_WGRAD_REDUCE=0 keeps the per-output kernel (A/B)
 static bool wgrad_reduce_rows(const float* ws, float* dw, float* db, int nsplit, int slab, int cout, int cin, int kd,
                               int taps2, int nco_t, int nci_t, int cot_w, int cit_w, int kd_bias, int perm_r,
                               float scale, int accumulate, hipStream_t s) {
-  static int mode = -1;
-  if (mode < 0) {
-    const char* e = getenv("VSRK_WGRAD_REDUCE");
-    mode = (e && e[0] == '0') ? 0 : 1;
-  }
   const int nblk_w = cout * nci_t * kd;
   // one lane sums all splits of an output: only for few splits and enough
   // workgroups (EDSR's 64 -> 64 has 256 splits over 64 such workgroups)
-  if (!mode || cit_w * taps2 > 64 * 9 || nsplit > 32 || nblk_w < 256) return false;
+  if (!g_wgrad_reduce || cit_w * taps2 > 64 * 9 || nsplit > 32 || nblk_w < 256) return false;
   const int nblk_b = db ? (int)ceil_div64(cout, 256) : 0;
   wgrad_reduce_rows_kernel<<<nblk_w + nblk_b, 256, 0, s>>>(ws, dw, db, nsplit, slab, cout, cin, kd, taps2, nco_t,
                                                             nci_t, cot_w, cit_w, kd_bias, perm_r, scale, accumulate,
@@ -447,11 +447,7 @@ static WgradPlan wgrad_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, cons
   // EDSR 64->64 wgrad 10 % (147 -> 133 us at 256 workgroups; DUF's 3x3x3,
   // at 24 tiles per workgroup, keeps its 512: 231 vs 324 us at 256).
   // VSRK_WGRAD_TARGET=<workgroups> overrides the rule (A/B only).
-  static int target = -1;
-  if (target < 0) {
-    const char* e = getenv("VSRK_WGRAD_TARGET");
-    target = e ? std::max(64, atoi(e)) : 0;
-  }
+  const int target = g_wgrad_target;
   // 3-D (kd > 1): about 64 tiles per workgroup (at least one workgroup per
   // CU).  The pipelined kernel's sweep (profiles/r2_wgrad_pipe_ab.txt): DUF
   // 64->32 at 64 x 7 x 128 x 128 fastest at ~1024 workgroups (~84 tiles

@@ -477,18 +477,17 @@ __global__ __attribute__((amdgpu_waves_per_eu(1, 1))) __launch_bounds__(GTHR) vo
   }
 }
 
+#ifdef VSRK_WP_EXP
+const int g_wp_ablate = vsrk_env_int("VSRK_WP_ABLATE", 0);  // measurement builds: the kernel's ABL forms
+#endif
+
 template <typename T, int NCO, int NCI, int PRO>
 void launch_pipe(const WgradArgs& a, hipStream_t s) {
   const size_t lds = WpGeom<NCO, NCI>::lds_bytes();
   auto kern = conv_wgrad_pipe_kernel<T, NCO, NCI, PRO, 0>;
 #ifdef VSRK_WP_EXP
-  static int abl = -1;
-  if (abl < 0) {
-    const char* e = getenv("VSRK_WP_ABLATE");
-    abl = e ? atoi(e) : 0;
-  }
-  if (abl == 1) kern = conv_wgrad_pipe_kernel<T, NCO, NCI, PRO, 1>;
-  if (abl == 2) kern = conv_wgrad_pipe_kernel<T, NCO, NCI, PRO, 2>;
+  if (g_wp_ablate == 1) kern = conv_wgrad_pipe_kernel<T, NCO, NCI, PRO, 1>;
+  if (g_wp_ablate == 2) kern = conv_wgrad_pipe_kernel<T, NCO, NCI, PRO, 2>;
 #endif
   (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   kern<<<a.nblk, GTHR, lds, s>>>(a);
@@ -521,22 +520,11 @@ bool pipe_t(const WgradArgs& a, int nco, int nci, hipStream_t s) {
 
 }  // namespace
 
-int vsrk_g_wgrad_pipe_mode = -1;  // -1: from VSRK_WGRAD_PIPE (default on), 0 off, 1 on (vsrk_conv_set_path)
-
-bool vsrk_wgrad_pipe_enabled() {
-  int mode = vsrk_g_wgrad_pipe_mode;
-  if (mode < 0) {
-    const char* e = getenv("VSRK_WGRAD_PIPE");
-    mode = (e && e[0] == '0') ? 0 : 1;
-  }
-  return mode != 0;
-}
-
 // 1 = launched (same slab layout as conv_wgrad_kernel); 0 = not eligible.
 // Eligible: 16-bit, kh = kw = 3, chunk-readable views (plain or sub-pixel),
 // whole 16-byte channel chunks, an (n, d) slice addressable in 30 bits.
 int vsrk_conv_wgrad_pipe(const WgradArgs& a, int nco, int nci, int dtype, hipStream_t s) {
-  if (!vsrk_wgrad_pipe_enabled()) return 0;
+  if (vsrk_path_mode(VSRK_PATH_WGRAD_PIPE) == 0) return 0;
   if (a.kh != 3 || a.kw != 3) return 0;
   if (!a.xvec || !a.dyvec) return 0;
   if (a.cin % 8 || a.cout % 8 || a.x.cphys % 8 || a.dy.cphys % 8) return 0;

@@ -28,7 +28,6 @@
 //    layout ([9 taps][32 co][32 ci] + dbias per kd "combo"), summed in a
 //    fixed order by wgrad_reduce_kernel.  dbias: an MFMA against ones on each
 //    dy slice once (workgroups of input chunk 0).
-#include <cstdlib>
 #include "conv_common.h"
 
 namespace {
@@ -511,38 +510,21 @@ extern "C" int vsrk_wroll_stamps(unsigned* dst) {
 namespace {
 #endif
 
-int g_wroll_mode = -1;  // -1: VSRK_WGRAD_ROLL (unset: 2), 0 off, 1 forced on, 2 automatic
-
-int wroll_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
-
 }  // namespace
-
-void vsrk_conv_set_wgrad_roll_mode(int mode) { g_wroll_mode = mode; }
 
 // The plan of the rolling weight gradient for a request, or false when the
 // request is not eligible.  Workspace: nsplit*2 x (3 * nci * nco) slabs of
 // (9 * 1024 + 32) floats.
 bool vsrk_wgrad_roll_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy, int* nsplit,
                           int* tps, int* ntiles, int* dzc, size_t* ws_bytes) {
-  if (g_wroll_mode < 0) {
-    const char* e = getenv("VSRK_WGRAD_ROLL");
-    g_wroll_mode = !e ? 2 : (e[0] == '0' ? 0 : 1);
-  }
-  if (g_wroll_mode == 0) return false;
+  const int mode = vsrk_path_mode(VSRK_PATH_WGRAD_ROLL);  // 0 off, 1 forced on, 2 automatic
+  if (mode == 0) return false;
   // automatic mode: with a single output depth the kd-tap reuse of the
   // rolling walk does not pay for its ring (DUF's last unit, 3 -> 1: 812 vs
   // 982 us for the pipelined kernel); at 3 output depths it does since the
   // round-5 loop order (DUF unit 5 at F = 192, 5 -> 3: 1495 vs 1703 us; it
   // lost, 1764 vs 1619, in round 3)
-  if (g_wroll_mode == 2 && dy->d <= 1 && vsrk_g_roll_dz == 0) return false;
+  if (mode == 2 && dy->d <= 1 && vsrk_g_roll_dz == 0) return false;
   if (!vsrk_is16(x->dtype) || dy->dtype != x->dtype) return false;
   if (d->kd != 3 || d->kh != 3 || d->kw != 3 || d->pd < 0 || d->pd > 2 || d->ph < 0 || d->ph > 2 || d->pw < 0 ||
       d->pw > 2)
@@ -561,7 +543,7 @@ bool vsrk_wgrad_roll_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, const 
   // depth runs: whole depth unless the grid would have < 1 tile per workgroup
   int z = dy->d;
   const int combos = nco * nci;
-  const int64_t want_wg = std::max<int64_t>(1, wroll_num_cus());
+  const int64_t want_wg = std::max<int64_t>(1, vsrk_num_cus());
   if (spatial * combos < want_wg) {
     const int64_t runs = std::min<int64_t>(ceil_div64(want_wg, spatial * combos), dy->d);
     z = (int)ceil_div64(dy->d, runs);
@@ -618,14 +600,7 @@ int vsrk_conv_wgrad_roll(const vsrk_conv_desc* d, const vsrk_tensor5* x, const v
   a.nco_tiles = dy->c / 32;
   a.slab = 9 * 1024 + 32;
   a.kd_bias = std::min(d->pd, 2);
-  {
-    static int prio = -1;
-    if (prio < 0) {
-      const char* e = getenv("VSRK_ROLL_PRIO");
-      prio = (e && e[0] == '1') ? 1 : 0;
-    }
-    a.prio = prio;
-  }
+  a.prio = vsrk_g_roll_prio;
   a.tiles_w = make_rdivw(ceil_div(dy->w, TW));
   a.tiles_h = make_rdivw(ceil_div(dy->h, WTH));
   a.nzc = make_rdivw(ceil_div(dy->d, dzc));

@@ -36,7 +36,6 @@
 //    ones, wave (half, quarter q) on k-chunk q (two per wave and stage), the
 //    four k-chunks' partials added through LDS at the end.
 #include <algorithm>
-#include <cstdlib>
 #include "conv_common.h"
 
 namespace {
@@ -357,28 +356,15 @@ __global__ __launch_bounds__(RW_NW * 64, 1) void wgrad_row_kernel(RowArgs a) {
   }
 }
 
-int g_wrow_mode = -1;  // -1: VSRK_WGRAD_ROW (unset: on), 0 off, 1 on, 2 on with the sub-pixel tap skip forms
-
-int wrow_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  }
-  return n;
-}
+// A/B knobs, read at load
+const int g_wrow_bands = std::max(0, vsrk_env_int("VSRK_WGRAD_ROW_BANDS", 0));  // > 0: bands per image column
+const int g_wrow_prio = vsrk_env_int("VSRK_WGRAD_ROW_PRIO", 0) == 1;            // RowArgs::prio
 
 }  // namespace
 
-void vsrk_conv_set_wgrad_row_mode(int mode) { g_wrow_mode = mode; }
-
 bool vsrk_wgrad_row_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy, VsrkRowPlan* p) {
-  if (g_wrow_mode < 0) {
-    const char* e = getenv("VSRK_WGRAD_ROW");
-    g_wrow_mode = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (g_wrow_mode == 0) return false;
+  const int mode = vsrk_path_mode(VSRK_PATH_WGRAD_ROW);  // 0 off, 1 on, 2 on with the sub-pixel tap skip forms
+  if (mode == 0) return false;
   if (!vsrk_is16(x->dtype) || dy->dtype != x->dtype) return false;
   if (d->kd != 1 || d->kh != 3 || d->kw != 3 || d->pd != 0 || d->ph != 1 || d->pw != 1) return false;
   // (sub-pixel views: one operand is a shuffle-r view of a high-res buffer;
@@ -391,7 +377,7 @@ bool vsrk_wgrad_row_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, const v
   // A/B, same box: projection weight gradients 25.3 ms/step here vs 22.0 on the
   // pipelined kernel (profiles/r5_wgrad_row_subpixel_ab.txt).  Plain
   // shuffled views (EDSR's up-sampler, all taps live) run here.
-  if (d->subpixel && (x->shuffle > 1 || dy->shuffle > 1) && g_wrow_mode != 2) return false;
+  if (d->subpixel && (x->shuffle > 1 || dy->shuffle > 1) && mode != 2) return false;
   if (x->c / 64 > RW_MAXB || dy->c / 64 > RW_MAXB) return false;
   for (const vsrk_tensor5* t : {x, dy}) {  // a sub-pixel view: every 64-channel block inside one phase
     if (t->shuffle <= 1) continue;
@@ -412,17 +398,10 @@ bool vsrk_wgrad_row_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, const v
   const int ncot = dy->c / RW_COW, ncic = x->c / 64;
   const int64_t per_band = images * nseg * ncot * ncic;  // workgroups per band of every image
   // about one workgroup per CU (the ring takes 100 KB): bands of >= 8 rows
-  int64_t want = std::max<int64_t>(1, wrow_num_cus());
+  int64_t want = std::max<int64_t>(1, vsrk_num_cus());
   if (vsrk_g_grid_cap > 0) want = std::min<int64_t>(want, vsrk_g_grid_cap);
   int bands = (int)std::max<int64_t>(1, std::min<int64_t>((want + per_band / 2) / per_band, ceil_div(x->h, 8)));
-  {
-    static int ov = -1;  // A/B knob: VSRK_WGRAD_ROW_BANDS=<bands per image column>
-    if (ov < 0) {
-      const char* e = getenv("VSRK_WGRAD_ROW_BANDS");
-      ov = e ? std::max(0, atoi(e)) : 0;
-    }
-    if (ov > 0) bands = std::min(ov, x->h);
-  }
+  if (g_wrow_bands > 0) bands = std::min(g_wrow_bands, x->h);
   if (vsrk_g_grid_cap > 0) bands = std::max(1, std::min(bands, x->h));
   p->band_h = ceil_div(x->h, bands);
   p->bands = ceil_div(x->h, p->band_h);
@@ -480,14 +459,7 @@ int vsrk_conv_wgrad_row(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vs
   a.ncic = p.ncic;
   a.nsplit = p.nsplit;
   a.want_bias = want_bias;
-  {
-    static int prio = -1;
-    if (prio < 0) {
-      const char* e = getenv("VSRK_WGRAD_ROW_PRIO");
-      prio = (e && e[0] == '1') ? 1 : 0;
-    }
-    a.prio = prio;
-  }
+  a.prio = g_wrow_prio;
   const int grid = p.nsplit * p.ncot * p.ncic;
   vsrk_dispatch16(x->dtype, [&](auto tag) {
     using H = decltype(tag);

@@ -24,13 +24,12 @@ int vsrk_conv_fwd_stencil(const vsrk_conv_desc* d, const vsrk_tensor5* x, const 
 int vsrk_conv_fwd_stencil_out(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed,
                               const float* bias, const vsrk_tensor5* residual, const vsrk_tensor5* mask,
                               const vsrk_tensor5* y, hipStream_t s);
-void vsrk_conv_set_stencil_mode(int mode);
 int vsrk_conv_fwd_thin(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed, const float* bias,
                        const float* pro_scale, const float* pro_shift, const vsrk_tensor5* residual,
                        const vsrk_tensor5* mask, const vsrk_tensor5* y, hipStream_t s);
 
 // rolling-depth 16-bit Conv3d 3x3x3 (conv_roll.hip): forward / data gradient;
-// same return convention; vsrk_conv_set_roll_mode: -1 env VSRK_CONV_ROLL, 0 off, 1 forced on, 2 automatic
+// same return convention; VSRK_PATH_ROLL: 0 off, 1 forced on, 2 automatic
 // slope_ws != nullptr (2-D forms): mask is a PReLU output y_fwd with y's
 // geometry and strides, desc->mask_slope its slope a: out = conv * (y_fwd > 0 ?
 // 1 : a) and per-lane partials of sum_{y_fwd < 0} out * y_fwd into slope_ws
@@ -62,22 +61,19 @@ int vsrk_conv_fwd_roll(const vsrk_conv_desc* d, const vsrk_tensor5* x, const voi
 int vsrk_roll_bnred_final(const vsrk_roll_bnred& r, int cout, float* sum_dy, float* sum_dy_xhat, hipStream_t s);
 size_t vsrk_roll_bnred_ws_floats(const vsrk_tensor5* y);
 size_t vsrk_roll_slope_ws_bytes();
-void vsrk_conv_set_roll_mode(int mode);
-void vsrk_conv_set_roll_wr_mode(int mode);
-void vsrk_conv_set_roll_fold_mode(int mode);
-// the depth-folded rolling forward (conv_roll_fold.hip): one output depth from
-// three slices; 1 launched, 0 not eligible, < 0 -(error status)
+// the depth-folded rolling forward (conv_roll_fold.hip: conv_roll_impl.h's
+// kernel built with 32-row tiles): one output depth from three slices; 1
+// launched, 0 not eligible, < 0 -(error status)
 int vsrk_conv_fwd_roll_fold(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed, const float* bias,
                             const float* pro_scale, const float* pro_shift, const vsrk_tensor5* y, hipStream_t s);
 
 // row-walking 16-bit Conv 3x3 64 -> 64 (conv_row.hip): forward / data gradient
 // of EDSR's body convs, reached from conv_roll.hip's 2-D branch after its
 // checks; 1 launched, 0 not eligible, < 0 -(error status).
-// vsrk_conv_set_row_mode: -1 default (VSRK_CONV_ROW, read at load time; unset:
-// the forms that measured faster than the tile kernel), 0 off, 1 every form
+// VSRK_PATH_ROW: -1 default (VSRK_CONV_ROW unset: the forms that measured
+// faster than the tile kernel), 0 off, 1 every form
 int vsrk_conv_fwd_row(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed, const float* bias,
                       const vsrk_tensor5* residual, const vsrk_tensor5* mask, const vsrk_tensor5* y, hipStream_t s);
-void vsrk_conv_set_row_mode(int mode);
 
 // pointwise (1x1x1) bf16 conv (conv_pw.hip): forward / data gradient and
 // weight gradient; same return convention (the wgrad launches its own reduce)
@@ -97,10 +93,41 @@ int vsrk_conv_wgrad_pw(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsr
                        const float* pro_scale, const float* pro_shift, float dy_scale, int32_t perm_r, float* dw,
                        float* dbias, int32_t accumulate, void* workspace, size_t workspace_bytes, hipStream_t s);
 
-// path switches (vsrk_conv_set_path): -1 = from the environment, 0 off, 1 on
-extern int vsrk_g_pw_mode;
-extern int vsrk_g_thin_mode;
-extern int vsrk_g_wgrad_pipe_mode;
+// ---- dispatch state (conv_paths.hip) ----
+// One mode per kernel family, resolved from the family's environment variable
+// when the library is loaded and changed only by vsrk_conv_set_path (the table
+// of names, variables and defaults is in conv_paths.hip): 0 off, 1 on; roll /
+// wgrad_roll 2 = automatic; roll_wr / wgrad_row 2 = the extra forms; row -1 =
+// the per-form default.  Process-wide test / A-B switches: set between
+// launches, never concurrently with them.
+enum vsrk_path {
+  VSRK_PATH_FAST,
+  VSRK_PATH_PW,
+  VSRK_PATH_PW_WIDE,
+  VSRK_PATH_ROLL,
+  VSRK_PATH_ROLL_WR,
+  VSRK_PATH_ROLL_FOLD,
+  VSRK_PATH_ROW,
+  VSRK_PATH_THIN,
+  VSRK_PATH_STENCIL,
+  VSRK_PATH_WGRAD_PIPE,
+  VSRK_PATH_WGRAD_ROLL,
+  VSRK_PATH_WGRAD_ROW,
+  VSRK_PATH_COUNT
+};
+extern int vsrk_g_path_mode[VSRK_PATH_COUNT];
+static inline int vsrk_path_mode(vsrk_path p) { return vsrk_g_path_mode[p]; }
+// environment helpers for the secondary A/B knobs, which are file-scope consts
+// initialised at load next to the code that uses them.  flag: unset = dflt, a
+// value starting with '0' = 0, any other value = 1.  int: unset = dflt, else atoi.
+int vsrk_env_flag(const char* name, int dflt);
+int vsrk_env_int(const char* name, int dflt);
+// CUs of the current device at the first call (256 when the query fails)
+int vsrk_num_cus();
+// VSRK_ROLL_PRIO=1 (A/B): s_setprio 1 for waves 4-7 of conv_roll and conv_wgrad_roll
+extern const int vsrk_g_roll_prio;
+// vsrk_conv_set_roll_depth: > 0 output depths per tile of both rolling kernels
+extern int vsrk_g_roll_dz;
 // vsrk_conv_set_grid_cap: > 0 caps the workgroups of the persistent conv grids
 // and of the weight-gradient split (tests drive the multi-tile loops with it)
 extern int vsrk_g_grid_cap;

@@ -408,19 +408,27 @@ def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, k, pad, dw: torch.Tensor, dbia
 
 
 def set_conv_path(path: str, mode: int) -> None:
-    """Select a conv kernel family ("fast", "pw", "pw_wide", "roll", "roll_wr", "roll_fold", "thin", "wgrad_pipe",
-    "wgrad_roll", "wgrad_row", "row", "stencil"):
-    -1 default, 0 off, 1 on
+    """Select a conv kernel family ("fast", "pw", "pw_wide", "roll", "roll_wr", "roll_fold", "row", "thin",
+    "stencil", "wgrad_pipe", "wgrad_roll", "wgrad_row"): 0 off, 1 on, -1 back
+    to the mode resolved from the family's environment variable when the
+    library was loaded (the table is in include/vsrk.h)
     (for "roll" / "wgrad_roll": 1 forces the rolling kernel on every eligible
     shape, the default also skips shallow output depths where it is slower;
     "wgrad_row": 2 also takes the sub-pixel tap-skip views; "roll_wr": the
     rolling conv's resident weights, 2 also with the prefetched residual / mask
     epilogue, where they are slower, and 0 or 2 keep the row kernel aside;
     "row": the row-walking 3x3 64 -> 64 conv of EDSR's body, reached through
-    "roll"; its default, read from VSRK_CONV_ROW when the library loads,
-    routes the epilogue forms that measured faster than the tile kernel, 1
-    routes every form it covers)."""
+    "roll"; its default routes the epilogue forms that measured faster than
+    the tile kernel, 1 routes every form it covers).  A process-wide test /
+    A-B switch: set it between launches, not concurrently with them."""
     N.check(_lib().vsrk_conv_set_path(path.encode(), int(mode)), "conv_set_path")
+
+
+def get_conv_path(path: str) -> int:
+    """The effective mode of a conv kernel family (see set_conv_path)."""
+    mode = C.c_int32()
+    N.check(_lib().vsrk_conv_get_path(path.encode(), C.byref(mode)), "conv_get_path")
+    return mode.value
 
 
 def set_roll_depth(depths: int) -> None:
