@@ -535,6 +535,54 @@ int vsrk_upsample_cl_bwd(const vsrk_tensor5* gy, const vsrk_tensor5* gx, int32_t
 int vsrk_tanh_fwd(const vsrk_tensor5* x, const vsrk_tensor5* y, void* stream);
 int vsrk_tanh_bwd(const vsrk_tensor5* y, const vsrk_tensor5* dy, const vsrk_tensor5* dx, void* stream);
 
+/* EDVR's TSA fusion operators (EDVR_arch.py:257-323) on plain channels-last
+ * (n, 1, h, w, c) views of fp32 / bf16 / fp16, one dtype per call, fp32
+ * arithmetic.  No atomics; every sum has a fixed order: bitwise reproducible.
+ * 16-byte accesses along the channel axis where c, the base pointers and the
+ * strides allow; one element per lane otherwise.
+ *
+ * Temporal attention (:284-294).  emb, aligned: (B*N, 1, h, w, C), frame i of
+ * batch b at index b*N + i; emb_ref: (B, 1, h, w, C), the centre frame's
+ * embedding; out: (B, 1, h, w, N*C), e.g. the fusion conv's input; prob: fp32
+ * (B, N, h, w) contiguous, saved for the backward.
+ *   cor(b,i,p)        = sum_c emb(b,i,p,c) * emb_ref(b,p,c)   (fp32, fixed order)
+ *   prob              = sigmoid(cor)
+ *   out(b,p,i*C + c)  = aligned(b,i,p,c) * prob(b,i,p)
+ * Backward, one launch, from gout in out's layout:
+ *   g_aligned = gout * prob;  gcor = (sum_c gout * aligned) * prob (1 - prob)
+ *   g_emb(b,i) = gcor_i * emb_ref(b);  g_emb_ref(b) = sum_i gcor_i * emb(b,i),
+ *   i ascending.
+ * A pixel's channels sit in neighbouring lanes and are summed with wavefront
+ * shuffles: at most 64 chunks (or, one element per lane, 64 channels) a pixel. */
+int vsrk_tsa_tatt_fwd(const vsrk_tensor5* emb, const vsrk_tensor5* emb_ref, const vsrk_tensor5* aligned,
+                      const vsrk_tensor5* out, float* prob, void* stream);
+int vsrk_tsa_tatt_bwd(const vsrk_tensor5* emb, const vsrk_tensor5* emb_ref, const vsrk_tensor5* aligned,
+                      const float* prob, const vsrk_tensor5* gout, const vsrk_tensor5* g_emb,
+                      const vsrk_tensor5* g_emb_ref, const vsrk_tensor5* g_aligned, void* stream);
+
+/* nn.MaxPool2d(3, 2, 1) and nn.AvgPool2d(3, 2, 1) of one input in one pass
+ * (:267-268, 301-308): x (n, 1, h, w, c) -> y (n, 1, (h-1)/2 + 1, (w-1)/2 + 1,
+ * 2c), stored [max | avg].  Max: padding counts as -inf; on exact ties the
+ * first maximum in row-major window order wins and a NaN wins over what
+ * precedes it (the rule of vsrk_max_pool2x2_fwd).  Avg: the fp32 row-major sum
+ * divided by 9 always (count_include_pad).  The backward takes gy in y's
+ * layout and is a gather per input pixel over the windows that cover it (at
+ * most four, row-major): it recomputes each window's arg-max from the saved
+ * input x and writes all of gx.  The routed max gradients are summed in the
+ * storage type, as torch's CPU kernel does; the avg part is summed in fp32. */
+int vsrk_pool3s2_fwd(const vsrk_tensor5* x, const vsrk_tensor5* y, void* stream);
+int vsrk_pool3s2_bwd(const vsrk_tensor5* x, const vsrk_tensor5* gy, const vsrk_tensor5* gx, void* stream);
+
+/* The sigmoid-gated merge (:317-320) on views of one shape:
+ *   out = fea * sigmoid(att) * 2 + att_add
+ *   gfea = 2 s g;  gatt = 2 s (1 - s) fea g;  gatt_add = g,  s = sigmoid(att),
+ * recomputed from fea and att.  gatt_add may be NULL (it is g itself). */
+int vsrk_tsa_modulate_fwd(const vsrk_tensor5* fea, const vsrk_tensor5* att, const vsrk_tensor5* att_add,
+                          const vsrk_tensor5* out, void* stream);
+int vsrk_tsa_modulate_bwd(const vsrk_tensor5* fea, const vsrk_tensor5* att, const vsrk_tensor5* g,
+                          const vsrk_tensor5* gfea, const vsrk_tensor5* gatt, const vsrk_tensor5* gatt_add,
+                          void* stream);
+
 const char* vsrk_last_error(void);
 const char* vsrk_version(void);
 

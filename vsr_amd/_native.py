@@ -108,6 +108,9 @@ _SIGS = {
     "vsrk_dcn_im2col": (C.c_int, [_P] * 6),
     "vsrk_dcn_col2im": (C.c_int, [_P] * 6),
     "vsrk_dcn_coord_grad": (C.c_int, [_P] * 8),
+    "vsrk_dcn_view_im2col": (C.c_int, [_P, _T5, _T5, _T5, _P]),
+    "vsrk_dcn_view_coord_grad": (C.c_int, [_P, _T5, _T5, _T5, _T5, _P]),
+    "vsrk_dcn_view_col2im": (C.c_int, [_P, _T5, _T5, _P, _P]),
     "vsrk_bn_finalize": (C.c_int, [_P, _P, C.c_double, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P,
                                    C.c_int32, _P]),
     "vsrk_bn_finalize_dcount": (C.c_int, [_P, _P, _P, C.c_double, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P,
@@ -145,6 +148,12 @@ _SIGS = {
     "vsrk_upsample_cl_bwd": (C.c_int, [_T5, _T5, C.c_int32, C.c_int32, C.c_int32, _P]),
     "vsrk_tanh_fwd": (C.c_int, [_T5, _T5, _P]),
     "vsrk_tanh_bwd": (C.c_int, [_T5, _T5, _T5, _P]),
+    "vsrk_tsa_tatt_fwd": (C.c_int, [_T5, _T5, _T5, _T5, _P, _P]),
+    "vsrk_tsa_tatt_bwd": (C.c_int, [_T5, _T5, _T5, _P, _T5, _T5, _T5, _T5, _P]),
+    "vsrk_pool3s2_fwd": (C.c_int, [_T5, _T5, _P]),
+    "vsrk_pool3s2_bwd": (C.c_int, [_T5, _T5, _T5, _P]),
+    "vsrk_tsa_modulate_fwd": (C.c_int, [_T5, _T5, _T5, _T5, _P]),
+    "vsrk_tsa_modulate_bwd": (C.c_int, [_T5, _T5, _T5, _T5, _T5, _T5, _P]),
     "vsrk_last_error": (C.c_char_p, []),
     "vsrk_version": (C.c_char_p, []),
 }

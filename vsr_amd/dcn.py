@@ -14,6 +14,10 @@ epilogue), its data gradient gives the column gradient and its weight
 gradient the weight / bias gradients; vsrk_dcn_col2im and
 vsrk_dcn_coord_grad return the input, offset and mask gradients.  Conv
 groups other than 1 are not supported (EDVR uses 1).
+
+EDVRNet (nets/edvr_net.py) does not go through this layer: it runs its DCN
+packs on channels-last views in fp32, bf16 or fp16 (the vsrk_dcn_view_*
+kernels).
 """
 from __future__ import annotations
 

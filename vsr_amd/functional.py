@@ -580,6 +580,116 @@ def tanh_bwd(y: torch.Tensor, dy: torch.Tensor, dx: torch.Tensor) -> torch.Tenso
     return dx
 
 
+def pool3s2(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """y = [nn.MaxPool2d(3, 2, 1)(x) | nn.AvgPool2d(3, 2, 1)(x)] of channels-last
+    x (N, 1, h, w, C) -> (N, 1, (h-1)//2 + 1, (w-1)//2 + 1, 2C), in one pass."""
+    xv, yv = N.t5(x), N.t5(y)
+    N.check(_lib().vsrk_pool3s2_fwd(C.byref(xv), C.byref(yv), N.stream_ptr(x.device)), "pool3s2_fwd")
+    return y
+
+
+def pool3s2_bwd(x: torch.Tensor, gy: torch.Tensor, gx: torch.Tensor) -> torch.Tensor:
+    """gx = the max half of gy routed to each window's arg-max (recomputed from
+    the pools' input x; the first maximum on ties) plus the avg half spread
+    over each window / 9: a fixed-order gather that writes all of gx."""
+    xv, gv, ov = N.t5(x), N.t5(gy), N.t5(gx)
+    N.check(_lib().vsrk_pool3s2_bwd(C.byref(xv), C.byref(gv), C.byref(ov), N.stream_ptr(x.device)), "pool3s2_bwd")
+    return gx
+
+
+def tsa_tatt(emb: torch.Tensor, emb_ref: torch.Tensor, aligned: torch.Tensor, out: torch.Tensor,
+             prob: torch.Tensor) -> torch.Tensor:
+    """EDVR's per-pixel temporal attention: emb, aligned (B*N, 1, h, w, C),
+    emb_ref (B, 1, h, w, C); out (B, 1, h, w, N*C) gets aligned * sigmoid(<emb,
+    emb_ref>) frame by frame, prob (B, N, h, w) fp32 the sigmoid (vsrk_tsa_tatt_fwd)."""
+    b, n = emb_ref.shape[0], emb.shape[0] // max(emb_ref.shape[0], 1)
+    if prob.dtype != torch.float32 or not prob.is_contiguous() or tuple(prob.shape) != (b, n, *emb.shape[2:4]):
+        raise ValueError(f"tsa_tatt_fwd: prob must be contiguous fp32 {(b, n, *emb.shape[2:4])}, got "
+                         f"{prob.dtype} {tuple(prob.shape)}")
+    ev, rv, av, ov = N.t5(emb), N.t5(emb_ref), N.t5(aligned), N.t5(out)
+    N.check(_lib().vsrk_tsa_tatt_fwd(C.byref(ev), C.byref(rv), C.byref(av), C.byref(ov), prob.data_ptr(),
+                                     N.stream_ptr(emb.device)), "tsa_tatt_fwd")
+    return out
+
+
+def tsa_tatt_bwd(emb: torch.Tensor, emb_ref: torch.Tensor, aligned: torch.Tensor, prob: torch.Tensor,
+                 gout: torch.Tensor, g_emb: torch.Tensor, g_emb_ref: torch.Tensor, g_aligned: torch.Tensor) -> None:
+    """The three gradients of tsa_tatt in one launch, from gout in out's layout
+    and the saved prob; g_emb_ref sums the frames in ascending order."""
+    b, n = emb_ref.shape[0], emb.shape[0] // max(emb_ref.shape[0], 1)
+    if prob.dtype != torch.float32 or not prob.is_contiguous() or tuple(prob.shape) != (b, n, *emb.shape[2:4]):
+        raise ValueError(f"tsa_tatt_bwd: prob must be contiguous fp32 {(b, n, *emb.shape[2:4])}, got "
+                         f"{prob.dtype} {tuple(prob.shape)}")
+    vs = [N.t5(t) for t in (emb, emb_ref, aligned, gout, g_emb, g_emb_ref, g_aligned)]
+    N.check(_lib().vsrk_tsa_tatt_bwd(C.byref(vs[0]), C.byref(vs[1]), C.byref(vs[2]), prob.data_ptr(), C.byref(vs[3]),
+                                     C.byref(vs[4]), C.byref(vs[5]), C.byref(vs[6]), N.stream_ptr(emb.device)),
+            "tsa_tatt_bwd")
+
+
+def tsa_modulate(fea: torch.Tensor, att: torch.Tensor, att_add: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out = fea * sigmoid(att) * 2 + att_add on views of one shape and dtype."""
+    vs = [N.t5(t) for t in (fea, att, att_add, out)]
+    N.check(_lib().vsrk_tsa_modulate_fwd(*(C.byref(v) for v in vs), N.stream_ptr(fea.device)), "tsa_modulate_fwd")
+    return out
+
+
+def tsa_modulate_bwd(fea: torch.Tensor, att: torch.Tensor, g: torch.Tensor, gfea: torch.Tensor, gatt: torch.Tensor,
+                     gatt_add: torch.Tensor | None = None) -> None:
+    """gfea = 2 s g, gatt = 2 s (1 - s) fea g with s = sigmoid(att), and, where a
+    view is given, gatt_add = g."""
+    vs = [N.t5(t) for t in (fea, att, g, gfea, gatt)]
+    ga = N.t5(gatt_add) if gatt_add is not None else None
+    N.check(_lib().vsrk_tsa_modulate_bwd(*(C.byref(v) for v in vs), C.byref(ga) if ga is not None else None,
+                                         N.stream_ptr(fea.device)), "tsa_modulate_bwd")
+
+
+def dcn_geometry(x: torch.Tensor, kernel_size=(3, 3), stride=(1, 1), padding=(1, 1), dilation=(1, 1),
+                 deformable_groups: int = 1):
+    """The int32[15] geometry of include/vsrk_dcn.h for a channels-last x
+    (N, 1, H, W, C), with the output size: (geometry, Ho, Wo)."""
+    n, _, h, w, c = x.shape
+    (kh, kw), (sh, sw), (ph, pw), (dh, dw) = kernel_size, stride, padding, dilation
+    ho = (h + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1
+    wo = (w + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1
+    return (C.c_int32 * 15)(n, h, w, c, ho, wo, kh, kw, sh, sw, ph, pw, dh, dw, deformable_groups), ho, wo
+
+
+def dcn_view_im2col(geo, x: torch.Tensor, om: torch.Tensor, cols: torch.Tensor) -> torch.Tensor:
+    """cols (N, 1, Ho, Wo, K*C) = sigmoid(mask logit) * bilinear(x, p + offset)
+    for channels-last x (N, 1, H, W, C) of fp32 / bf16 / fp16, offsets and mask
+    logits read from om (N, 1, Ho, Wo, 3*G*K) fp32, the raw output of
+    conv_offset_mask (vsrk_dcn_view_im2col)."""
+    xv, ov, cv = N.t5(x), N.t5(om), N.t5(cols)
+    N.check(_lib().vsrk_dcn_view_im2col(geo, C.byref(xv), C.byref(ov), C.byref(cv), N.stream_ptr(x.device)),
+            "dcn_view_im2col")
+    return cols
+
+
+def dcn_view_coord_grad(geo, x: torch.Tensor, gcols: torch.Tensor, om: torch.Tensor, gom: torch.Tensor) -> torch.Tensor:
+    """gom = the gradient of dcn_view_im2col with respect to the raw om (offsets
+    and mask logits), given gcols: fixed order, bitwise reproducible."""
+    xv, cv, ov, gv = N.t5(x), N.t5(gcols), N.t5(om), N.t5(gom)
+    N.check(_lib().vsrk_dcn_view_coord_grad(geo, C.byref(xv), C.byref(cv), C.byref(ov), C.byref(gv),
+                                            N.stream_ptr(x.device)), "dcn_view_coord_grad")
+    return gom
+
+
+def dcn_view_col2im(geo, gcols: torch.Tensor, om: torch.Tensor, grad_x: torch.Tensor) -> torch.Tensor:
+    """grad_x += the scatter of gcols: grad_x is a contiguous fp32 (N, H, W, C)
+    (or (N, 1, H, W, C)) buffer the caller has zeroed.  Float atomics: the sum's
+    order, and so its last bits, can change from run to run."""
+    n, h, w, c = geo[0], geo[1], geo[2], geo[3]
+    if grad_x.dtype != torch.float32 or not grad_x.is_contiguous() or grad_x.numel() != n * h * w * c:
+        raise ValueError(f"dcn_view_col2im: grad_x must be contiguous fp32 with {(n, h, w, c)} elements, got "
+                         f"{grad_x.dtype} {tuple(grad_x.shape)}")
+    if grad_x.device != gcols.device:
+        raise RuntimeError("dcn_view_col2im: grad_x and gcols are on different devices")
+    cv, ov = N.t5(gcols), N.t5(om)
+    N.check(_lib().vsrk_dcn_view_col2im(geo, C.byref(cv), C.byref(ov), grad_x.data_ptr(), N.stream_ptr(gcols.device)),
+            "dcn_view_col2im")
+    return grad_x
+
+
 PADDING_MODES = {"zeros": 0, "border": 1}
 
 

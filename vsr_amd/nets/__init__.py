@@ -5,7 +5,8 @@ from .bicubic import Bicubic
 from .drf_net import DRFNet, DRFSISRNet
 from .duf_net import DUFNet
 from .edsr_net import EDSRNet
+from .edvr_net import EDVRNet
 from .frvsr_net import FRVSRNet
 from .srfb_net import SRFBNet
 
-__all__ = ["BaseNet", "EDSRNet", "DUFNet", "DRFNet", "DRFSISRNet", "SRFBNet", "Bicubic", "FRVSRNet"]
+__all__ = ["BaseNet", "EDSRNet", "DUFNet", "DRFNet", "DRFSISRNet", "SRFBNet", "Bicubic", "FRVSRNet", "EDVRNet"]

@@ -28,6 +28,9 @@ converts in and out (the fused generators avoid that).
       the flow gradient (none for the image)
   vsrk::max_pool2x2(x)
       nn.MaxPool2d(2) on (N, C, H, W)
+  vsrk::pool3s2(x)
+      nn.MaxPool2d(3, 2, 1) and nn.AvgPool2d(3, 2, 1) of (N, C, H, W) in one
+      pass, concatenated on the channel axis (EDVR's TSA pyramid)
   vsrk::duf_dynfilter(x, logits, residual, k, r)   DUF dynamic upsampling
   vsrk::loss(out, target, kind, param)             L1 / MSE / Huber / Charbonnier
   vsrk::psnr(out, target, mean, std, max_value, denormalize) -> per-sample
@@ -446,6 +449,49 @@ def _pool_bwd(ctx, grad):
 
 
 max_pool2x2.register_autograd(_pool_bwd, setup_context=_pool_setup)
+
+
+# ----------------------------------------------- 3x3 stride-2 pool pair --
+@torch.library.custom_op("vsrk::pool3s2", mutates_args=())
+def pool3s2(x: Tensor) -> Tensor:
+    """torch.cat((nn.MaxPool2d(3, 2, 1)(x), nn.AvgPool2d(3, 2, 1)(x)), 1) on (N, C,
+    H, W) in one pass (EDVR_arch.py:267-268, 301-308): (N, 2C, (H-1)//2 + 1,
+    (W-1)//2 + 1)."""
+    if x.dim() != 4:
+        raise ValueError(f"vsrk::pool3s2 expects (N, C, H, W), got {tuple(x.shape)}")
+    xv = _to_cl(x, x.dtype)
+    n, d, h, w, c = xv.shape
+    yv = _empty_cl((n, d, (h - 1) // 2 + 1, (w - 1) // 2 + 1), 2 * c, x.dtype, x.device)
+    F.pool3s2(xv, yv)
+    return _from_cl(yv, True, x.dtype)
+
+
+@pool3s2.register_fake
+def _(x):
+    n, c, h, w = x.shape
+    return x.new_empty((n, 2 * c, (h - 1) // 2 + 1, (w - 1) // 2 + 1))
+
+
+@torch.library.custom_op("vsrk::pool3s2_backward", mutates_args=())
+def pool3s2_backward(grad: Tensor, x: Tensor) -> Tensor:
+    """grad_x of vsrk::pool3s2: the max half routed to each window's first
+    maximum plus the avg half spread over each window / 9."""
+    xv, gv = _to_cl(x, x.dtype), _to_cl(grad, x.dtype)
+    dxv = _empty_cl(xv.shape[:-1], xv.shape[-1], x.dtype, x.device)
+    F.pool3s2_bwd(xv, gv, dxv)
+    return _from_cl(dxv, True, x.dtype)
+
+
+@pool3s2_backward.register_fake
+def _(grad, x):
+    return x.new_empty(x.shape)
+
+
+def _pool3s2_bwd(ctx, grad):
+    return pool3s2_backward(grad.contiguous(), ctx.saved_tensors[0])
+
+
+pool3s2.register_autograd(_pool3s2_bwd, setup_context=_pool_setup)
 
 
 # ----------------------------------------------------------- DUF filter --
