@@ -108,23 +108,25 @@ def _run(x, om, gcols, G, dtype):
     return geo, cols, gom, gx
 
 
-def _plane_kernels(geo, x, om, gcols, G):
-    """The existing fp32 NCHW-plane kernels on the decoded planes, in the view kernels' layouts."""
+def _plane_kernels(geo, x, om, gcols, G, modulated=True):
+    """The fp32 NCHW-plane entry points on the decoded planes, in the view kernels' layouts; without
+    `modulated` as DCNv1 (mask and grad_mask NULL), the gradient then that of the offsets alone."""
     lib = N.load()
     n, _, h, w, c = x.shape
     offset, mask = (t.contiguous().to(DEV) for t in _decode(om, G))
+    if not modulated:
+        mask = None
     xd, gd = x.to(DEV), gcols.to(DEV)
     sp = N.stream_ptr(xd.device)
     cols = torch.empty((n, 1, h, w, K * c), device=DEV)
-    N.check(lib.vsrk_dcn_im2col(geo, xd.data_ptr(), offset.data_ptr(), mask.data_ptr(), cols.data_ptr(), sp), "im2col")
-    goff, gmask = torch.empty_like(offset), torch.empty_like(mask)
-    N.check(lib.vsrk_dcn_coord_grad(geo, xd.data_ptr(), gd.data_ptr(), offset.data_ptr(), mask.data_ptr(),
-                                    goff.data_ptr(), gmask.data_ptr(), sp), "coord_grad")
+    N.check(lib.vsrk_dcn_im2col(geo, xd.data_ptr(), offset.data_ptr(), N.ptr(mask), cols.data_ptr(), sp), "im2col")
+    goff, gmask = torch.empty_like(offset), torch.empty_like(mask) if modulated else None
+    N.check(lib.vsrk_dcn_coord_grad(geo, xd.data_ptr(), gd.data_ptr(), offset.data_ptr(), N.ptr(mask),
+                                    goff.data_ptr(), N.ptr(gmask), sp), "coord_grad")
     gx = torch.zeros_like(xd)
-    N.check(lib.vsrk_dcn_col2im(geo, gd.data_ptr(), offset.data_ptr(), mask.data_ptr(), gx.data_ptr(), sp), "col2im")
-    glogit = gmask * mask * (1 - mask)
-    gom = torch.cat((goff, glogit), 1).permute(0, 2, 3, 1).unsqueeze(1)
-    return cols, gom, gx
+    N.check(lib.vsrk_dcn_col2im(geo, gd.data_ptr(), offset.data_ptr(), N.ptr(mask), gx.data_ptr(), sp), "col2im")
+    gom = torch.cat((goff, gmask * mask * (1 - mask)), 1) if modulated else goff
+    return cols, gom.permute(0, 2, 3, 1).unsqueeze(1), gx
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -164,6 +166,30 @@ def test_view_kernels_match_fp64(shape, kind):
             _close(gx, px.double().cpu(), dtype, "gx vs planes " + what)
             part = slice(2 * G * K, None) if kind == "zero" else slice(None)
             _close(gom[..., part], pg[..., part].double().cpu(), dtype, "gom vs planes " + what)
+
+
+@pytest.mark.parametrize("shape", [(2, 8, 2, 4, 5), (1, 16, 1, 2, 3)], ids=lambda s: "x".join(map(str, s)))
+def test_plane_and_view_entry_points_run_one_core(shape):
+    """One sampling core behind two sample sources.  Mask logits of +20 make the view path's modulation
+    exactly 1 in fp32 (1 + expf(-20) rounds to 1), which is what the plane path takes for a NULL mask (DCNv1):
+    both then do the same arithmetic on the same numbers, so the columns and the offset gradient are equal bit
+    for bit and the logit gradient, vm * (1 * (1 - 1)), is exactly zero.  The atomic input scatter is compared
+    at the fp32 bound.  C / G = 4 puts one fp32 chunk in each deformable group (and 720 lanes in more than one
+    workgroup); 2 x 3 is the smallest map on which all nine taps leave the image."""
+    n, c, G, h, w = shape
+    g = torch.Generator().manual_seed(sum(p * q for p, q in zip(shape, (1, 10, 100, 1000, 10000))))
+    om = _make_om(g, n, G, h, w, "leaving")
+    om[..., 2 * G * K:] = 20.0
+    for p in _positions(om, G, h, w):  # the margin, per sample, on the fp32 values the kernels read
+        assert ((p - p.round()).abs() >= MARGIN - 1e-5).all()
+    x = torch.randn((n, 1, h, w, c), generator=g)
+    gcols = torch.randn((n, 1, h, w, K * c), generator=g)
+    geo, cols, gom, gx = _run(x, om, gcols, G, torch.float32)
+    pc, pg, px = _plane_kernels(geo, x, om, gcols, G, modulated=False)
+    assert torch.equal(cols, pc)
+    assert torch.equal(gom[..., :2 * G * K], pg)
+    assert (gom[..., 2 * G * K:] == 0).all()
+    _close(gx, px.double().cpu(), torch.float32, f"gx vs planes {shape}")
 
 
 @pytest.mark.parametrize("off", [8, 3])

@@ -638,16 +638,13 @@ int reduce_launch(int mode, const vsrk_tensor5* x, const vsrk_tensor5* dz, const
   View vg = dz ? make_view(dz) : vx;
   float* part = (float*)ws;
   const int thr = cpv * vpb;
-  if (x->dtype == VSRK_BF16) {
-    if (mode == 0) chan_reduce_kernel<bf16, 0><<<nblk, thr, 0, s>>>(vx, vg, scale, shift, mean, invstd, rpg, bpg, rpb, part);
-    else chan_reduce_kernel<bf16, 1><<<nblk, thr, 0, s>>>(vx, vg, scale, shift, mean, invstd, rpg, bpg, rpb, part);
-  } else if (x->dtype == VSRK_F16) {
-    if (mode == 0) chan_reduce_kernel<f16, 0><<<nblk, thr, 0, s>>>(vx, vg, scale, shift, mean, invstd, rpg, bpg, rpb, part);
-    else chan_reduce_kernel<f16, 1><<<nblk, thr, 0, s>>>(vx, vg, scale, shift, mean, invstd, rpg, bpg, rpb, part);
-  } else {
-    if (mode == 0) chan_reduce_kernel<float, 0><<<nblk, thr, 0, s>>>(vx, vg, scale, shift, mean, invstd, rpg, bpg, rpb, part);
-    else chan_reduce_kernel<float, 1><<<nblk, thr, 0, s>>>(vx, vg, scale, shift, mean, invstd, rpg, bpg, rpb, part);
-  }
+  vsrk_dispatch_dtype(x->dtype, [&](auto tag) {
+    using T = decltype(tag);
+    if (mode == 0)
+      chan_reduce_kernel<T, 0><<<nblk, thr, 0, s>>>(vx, vg, scale, shift, mean, invstd, rpg, bpg, rpb, part);
+    else
+      chan_reduce_kernel<T, 1><<<nblk, thr, 0, s>>>(vx, vg, scale, shift, mean, invstd, rpg, bpg, rpb, part);
+  });
   VSRK_LAUNCH_CHECK("bn_reduce");
   chan_final_kernel<<<dim3(x->c, groups), 256, 0, s>>>(part, bpg, x->c, o1, o2);
   VSRK_LAUNCH_CHECK("bn_reduce_final");
@@ -736,18 +733,11 @@ extern "C" int vsrk_bn_relu_bwd_apply(const vsrk_tensor5* x, const vsrk_tensor5*
   const int thr = cpv * (256 / cpv);
   const int grid = std::min(nrows, 4096);
   hipStream_t s = (hipStream_t)stream;
-  if (x->dtype == VSRK_BF16)
-    bn_relu_bwd_apply_kernel<bf16><<<grid, thr, 0, s>>>(make_view(x), make_view(dz), make_view(dx), scale, shift,
-                                                        mean, invstd, gamma, sum_dy, sum_dy_xhat,
-                                                        (float)(1.0 / count), nrows, accumulate);
-  else if (x->dtype == VSRK_F16)
-    bn_relu_bwd_apply_kernel<f16><<<grid, thr, 0, s>>>(make_view(x), make_view(dz), make_view(dx), scale, shift,
-                                                        mean, invstd, gamma, sum_dy, sum_dy_xhat,
-                                                        (float)(1.0 / count), nrows, accumulate);
-  else
-    bn_relu_bwd_apply_kernel<float><<<grid, thr, 0, s>>>(make_view(x), make_view(dz), make_view(dx), scale, shift,
-                                                         mean, invstd, gamma, sum_dy, sum_dy_xhat,
-                                                         (float)(1.0 / count), nrows, accumulate);
+  vsrk_dispatch_dtype(x->dtype, [&](auto tag) {
+    bn_relu_bwd_apply_kernel<decltype(tag)><<<grid, thr, 0, s>>>(make_view(x), make_view(dz), make_view(dx), scale,
+                                                                 shift, mean, invstd, gamma, sum_dy, sum_dy_xhat,
+                                                                 (float)(1.0 / count), nrows, accumulate);
+  });
   VSRK_LAUNCH_CHECK("bn_relu_bwd_apply");
   return VSRK_OK;
 }
@@ -792,9 +782,7 @@ extern "C" int vsrk_bn_relu_bwd_apply_multi(const vsrk_tensor5* x, const vsrk_te
       default: launch_apply_multi<T, 8>(x, dx, accumulate, cs, grid, thr, nrows, s); break;
     }
   };
-  if (x->dtype == VSRK_BF16) go(bf16{});
-  else if (x->dtype == VSRK_F16) go(f16{});
-  else go(float{});
+  vsrk_dispatch_dtype(x->dtype, go);
   VSRK_LAUNCH_CHECK("bn_relu_bwd_apply_multi");
   return VSRK_OK;
 }
@@ -815,12 +803,9 @@ extern "C" int vsrk_bn_apply(const vsrk_tensor5* x, const float* scale, const fl
   const int thr = cpv * (256 / cpv);
   const int grid = std::min(nrows, 4096);
   hipStream_t s = (hipStream_t)stream;
-  if (x->dtype == VSRK_BF16)
-    bn_apply_kernel<bf16><<<grid, thr, 0, s>>>(make_view(x), make_view(y), scale, shift, relu, nrows);
-  else if (x->dtype == VSRK_F16)
-    bn_apply_kernel<f16><<<grid, thr, 0, s>>>(make_view(x), make_view(y), scale, shift, relu, nrows);
-  else
-    bn_apply_kernel<float><<<grid, thr, 0, s>>>(make_view(x), make_view(y), scale, shift, relu, nrows);
+  vsrk_dispatch_dtype(x->dtype, [&](auto tag) {
+    bn_apply_kernel<decltype(tag)><<<grid, thr, 0, s>>>(make_view(x), make_view(y), scale, shift, relu, nrows);
+  });
   VSRK_LAUNCH_CHECK("bn_apply");
   return VSRK_OK;
 }

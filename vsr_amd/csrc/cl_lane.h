@@ -3,7 +3,8 @@
 // of the channel axis (8 x 16-bit or 4 x fp32 channels), consecutive lanes
 // consecutive chunks, then consecutive pixels; views whose channel count, base
 // or strides do not allow 16-byte accesses take the same kernels one element
-// per lane.
+// per lane.  The host layer of those kernels is here too: the argument checks
+// of a view and the launch over (storage type, lane width).
 #pragma once
 #include "vsrk_common.h"
 
@@ -11,6 +12,8 @@ namespace vsrk_cl {
 
 // what one lane moves: a 16-byte chunk (VEC) or a single element
 template <typename T, bool VEC> struct Lane {
+  using Elem = T;
+  static constexpr bool Vec = VEC;
   static constexpr int E = VEC ? Chunk<T>::E : 1;
   __device__ static __forceinline__ void load(const T* p, float* f) {
     if constexpr (VEC)
@@ -60,22 +63,57 @@ __device__ __forceinline__ int64_t off(const View& v, int n, int y, int x, int c
 // a > b as torch's max-pool compares: a NaN beats everything before it
 __device__ __forceinline__ bool beats(float a, float b) { return a > b || a != a; }
 
+// ---- host side: argument checks ----
+#define VSRK_TRY(expr)              \
+  do {                              \
+    const int rc_ = (expr);         \
+    if (rc_ != VSRK_OK) return rc_; \
+  } while (0)
+
+// A plain (n, 1, h, w, c) view of a known dtype.  `sized`: with a map that is not empty and at most 2^39
+// elements (one lane per chunk in 256-thread workgroups: the grid is a 32-bit count); the entry points that
+// check a pair of maps (resample_cl.hip) or a geometry (dcn.hip) make these two checks there.
+inline int check_view(const char* name, const vsrk_tensor5* t, bool sized = true) {
+  VSRK_CHECK(t && t->ptr, "%s: null argument", name);
+  VSRK_CHECK(t->dtype == VSRK_F32 || t->dtype == VSRK_BF16 || t->dtype == VSRK_F16, "%s: unknown dtype %d", name,
+             t->dtype);
+  VSRK_CHECK(t->shuffle <= 1, "%s: plain views only", name);
+  const int lo = sized ? 1 : 0;
+  VSRK_CHECK(t->n >= 1 && t->d == 1 && t->h >= lo && t->w >= lo && t->c >= 1,
+             "%s: view (%d, %d, %d, %d, %d) must be (n, 1, h, w, c)%s", name, t->n, t->d, t->h, t->w, t->c,
+             sized ? ", not empty" : "");
+  VSRK_CHECK(!sized || (int64_t)t->n * t->h * t->w * t->c <= ((int64_t)1 << 39), "%s: tensor too large", name);
+  return VSRK_OK;
+}
+
+// `t` (`what` in the message) is such a view, of this dtype and this (n, h, w, c)
+inline int check_shape(const char* name, const char* what, const vsrk_tensor5* t, int dtype, int n, int h, int w,
+                       int c, bool sized = true) {
+  VSRK_TRY(check_view(name, t, sized));
+  VSRK_CHECK(t->dtype == dtype, "%s: %s has dtype %d, expected %d", name, what, t->dtype, dtype);
+  VSRK_CHECK(t->n == n && t->h == h && t->w == w && t->c == c,
+             "%s: %s is (%d, 1, %d, %d, %d) and does not match the expected (%d, 1, %d, %d, %d)", name, what, t->n,
+             t->h, t->w, t->c, n, h, w, c);
+  return VSRK_OK;
+}
+
+// ---- host side: launch ----
+// lanes that cover c channels
+inline int chunks(int dtype, bool vec, int c) { return c / (vec ? 16 / vsrk_esize(dtype) : 1); }
+
+// Calls launch(Lane<T, VEC>{}, grid, s) with the grid of `lanes` lanes in 256-thread workgroups: the caller's
+// generic lambda names its kernel, K<typename L::Elem, L::Vec><<<grid, 256, 0, s>>>(...) with L = decltype(lane).
+template <typename T, typename Fn>
+inline void launch_lanes_of(bool vec, int64_t lanes, void* stream, Fn&& launch) {
+  const dim3 grid((unsigned)ceil_div64(lanes, 256));
+  if (vec) launch(Lane<T, true>{}, grid, (hipStream_t)stream);
+  else launch(Lane<T, false>{}, grid, (hipStream_t)stream);
+}
+// ... T the storage type of `dtype`
+template <typename Fn>
+inline void launch_lanes(int dtype, bool vec, int64_t lanes, void* stream, Fn&& launch) {
+  vsrk_dispatch_dtype(dtype, [&](auto tag) { launch_lanes_of<decltype(tag)>(vec, lanes, stream, launch); });
+}
+
 }  // namespace vsrk_cl
 
-// launch K<T, VEC> over `lanes` = voxels x chunks on the stream `s`
-#define VSRK_CL_LAUNCH(KERNEL, dtype, vec, voxels, c, ...)                                     \
-  do {                                                                                         \
-    const int E_ = (vec) ? 16 / vsrk_esize(dtype) : 1, nc = (c) / E_;                          \
-    const int64_t total = (int64_t)(voxels) * nc;                                              \
-    const dim3 grid((unsigned)ceil_div64(total, 256));                                         \
-    if ((dtype) == VSRK_BF16) {                                                                \
-      if (vec) KERNEL<bf16, true><<<grid, 256, 0, s>>>(__VA_ARGS__, nc, total);                \
-      else KERNEL<bf16, false><<<grid, 256, 0, s>>>(__VA_ARGS__, nc, total);                   \
-    } else if ((dtype) == VSRK_F16) {                                                          \
-      if (vec) KERNEL<f16, true><<<grid, 256, 0, s>>>(__VA_ARGS__, nc, total);                 \
-      else KERNEL<f16, false><<<grid, 256, 0, s>>>(__VA_ARGS__, nc, total);                    \
-    } else {                                                                                   \
-      if (vec) KERNEL<float, true><<<grid, 256, 0, s>>>(__VA_ARGS__, nc, total);               \
-      else KERNEL<float, false><<<grid, 256, 0, s>>>(__VA_ARGS__, nc, total);                  \
-    }                                                                                          \
-  } while (0)

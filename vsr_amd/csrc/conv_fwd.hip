@@ -337,13 +337,10 @@ __global__ __launch_bounds__(NTHR) void conv_fwd_kernel(ConvArgs a) {
 // ---------------------------------------------------------------------------
 // weight packing
 // ---------------------------------------------------------------------------
-template <typename T>
-__global__ void pack_weight_kernel(const float* __restrict__ w, T* __restrict__ out, int cout, int cin,
-                                   int kd, int kh, int kw, int mode, int perm_r, int co_pad,
-                                   int ci_pad, int64_t total) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  // out index = ((tap * co_pad + o) * ci_pad + i) in the packed (primed) roles
+// The value at packed index idx = ((tap * co_pad + o) * ci_pad + i), in the packed (primed) roles: the weight
+// element it comes from, or 0 in the padding.
+__device__ __forceinline__ float pack_source(const float* __restrict__ w, int64_t idx, int cout, int cin, int kd,
+                                             int kh, int kw, int mode, int perm_r, int co_pad, int ci_pad) {
   const int i = idx % ci_pad;
   const int64_t t1 = idx / ci_pad;
   const int o = t1 % co_pad;
@@ -355,17 +352,23 @@ __global__ void pack_weight_kernel(const float* __restrict__ w, T* __restrict__ 
   } else {
     co = i; ci = o; sd = kd - 1 - kdi; sh = kh - 1 - khi; sw = kw - 1 - kwi;
   }
-  float v = 0.f;
-  if (co < cout && ci < cin) {
-    int cot = co;
-    if (perm_r > 1) {  // view order (sub, c') -> torch order c'*r*r + sub
-      const int rr = perm_r * perm_r, cp = cout / rr;
-      const int sub = co / cp, cc = co - sub * cp;
-      cot = cc * rr + sub;
-    }
-    v = w[((((int64_t)cot * cin + ci) * kd + sd) * kh + sh) * kw + sw];
+  if (co >= cout || ci >= cin) return 0.f;
+  int cot = co;
+  if (perm_r > 1) {  // view order (sub, c') -> torch order c'*r*r + sub
+    const int rr = perm_r * perm_r, cp = cout / rr;
+    const int sub = co / cp, cc = co - sub * cp;
+    cot = cc * rr + sub;
   }
-  out[idx] = from_f32<T>(v);
+  return w[((((int64_t)cot * cin + ci) * kd + sd) * kh + sh) * kw + sw];
+}
+
+template <typename T>
+__global__ void pack_weight_kernel(const float* __restrict__ w, T* __restrict__ out, int cout, int cin,
+                                   int kd, int kh, int kw, int mode, int perm_r, int co_pad,
+                                   int ci_pad, int64_t total) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  out[idx] = from_f32<T>(pack_source(w, idx, cout, cin, kd, kh, kw, mode, perm_r, co_pad, ci_pad));
 }
 
 // one launch for many weights: blockIdx.y = weight, grid-stride in x
@@ -375,30 +378,8 @@ __global__ void pack_weights_kernel(const vsrk_pack_desc* __restrict__ descs) {
   const int co_pad = round_up(d.mode == 0 ? d.cout : d.cin, 128), ci_pad = round_up(d.mode == 0 ? d.cin : d.cout, 32);
   const int64_t total = (int64_t)d.kd * d.kh * d.kw * co_pad * ci_pad;
   T* out = reinterpret_cast<T*>(d.packed);
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int i = idx % ci_pad;
-    const int64_t t1 = idx / ci_pad;
-    const int o = t1 % co_pad;
-    const int tap = t1 / co_pad;
-    const int kwi = tap % d.kw, khi = (tap / d.kw) % d.kh, kdi = tap / (d.kw * d.kh);
-    int co, ci, sd, sh, sw;
-    if (d.mode == 0) {
-      co = o; ci = i; sd = kdi; sh = khi; sw = kwi;
-    } else {
-      co = i; ci = o; sd = d.kd - 1 - kdi; sh = d.kh - 1 - khi; sw = d.kw - 1 - kwi;
-    }
-    float v = 0.f;
-    if (co < d.cout && ci < d.cin) {
-      int cot = co;
-      if (d.perm_r > 1) {
-        const int rr = d.perm_r * d.perm_r, cp = d.cout / rr;
-        const int sub = co / cp, cc = co - sub * cp;
-        cot = cc * rr + sub;
-      }
-      v = d.w[((((int64_t)cot * d.cin + ci) * d.kd + sd) * d.kh + sh) * d.kw + sw];
-    }
-    out[idx] = from_f32<T>(v);
-  }
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x)
+    out[idx] = from_f32<T>(pack_source(d.w, idx, d.cout, d.cin, d.kd, d.kh, d.kw, d.mode, d.perm_r, co_pad, ci_pad));
 }
 
 }  // namespace
@@ -420,15 +401,11 @@ extern "C" int vsrk_conv_pack_weight(int32_t dtype, const float* w, int32_t cout
   const int blk = 256;
   const int grid = (int)ceil_div64(total, blk);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == VSRK_BF16)
-    pack_weight_kernel<bf16><<<grid, blk, 0, s>>>(w, (bf16*)packed, cout, cin, kd, kh, kw, mode, perm_r,
-                                                  co_pad, ci_pad, total);
-  else if (dtype == VSRK_F16)
-    pack_weight_kernel<f16><<<grid, blk, 0, s>>>(w, (f16*)packed, cout, cin, kd, kh, kw, mode, perm_r,
-                                                 co_pad, ci_pad, total);
-  else
-    pack_weight_kernel<float><<<grid, blk, 0, s>>>(w, (float*)packed, cout, cin, kd, kh, kw, mode, perm_r,
-                                                   co_pad, ci_pad, total);
+  vsrk_dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    pack_weight_kernel<T><<<grid, blk, 0, s>>>(w, (T*)packed, cout, cin, kd, kh, kw, mode, perm_r, co_pad, ci_pad,
+                                               total);
+  });
   VSRK_LAUNCH_CHECK("conv_pack_weight");
   return VSRK_OK;
 }
@@ -439,9 +416,7 @@ extern "C" int vsrk_conv_pack_weights(int32_t dtype, int32_t n, const vsrk_pack_
   if (n == 0 || max_elems == 0) return VSRK_OK;
   const int gx = (int)std::min<int64_t>(ceil_div64(max_elems, 256), 256);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == VSRK_BF16) pack_weights_kernel<bf16><<<dim3(gx, n), 256, 0, s>>>(descs);
-  else if (dtype == VSRK_F16) pack_weights_kernel<f16><<<dim3(gx, n), 256, 0, s>>>(descs);
-  else pack_weights_kernel<float><<<dim3(gx, n), 256, 0, s>>>(descs);
+  vsrk_dispatch_dtype(dtype, [&](auto tag) { pack_weights_kernel<decltype(tag)><<<dim3(gx, n), 256, 0, s>>>(descs); });
   VSRK_LAUNCH_CHECK("conv_pack_weights");
   return VSRK_OK;
 }

@@ -229,12 +229,9 @@ extern "C" int vsrk_prelu_wgrad(const vsrk_tensor5* y, const vsrk_tensor5* dx, c
   const int64_t nvox = (int64_t)y->n * y->d * y->h * y->w;
   hipStream_t s = (hipStream_t)stream;
   double* part = (double*)workspace;
-  if (y->dtype == VSRK_BF16)
-    prelu_partial_kernel<bf16><<<PRELU_BLOCKS, 256, 0, s>>>(vy, vd, nvox, part);
-  else if (y->dtype == VSRK_F16)
-    prelu_partial_kernel<f16><<<PRELU_BLOCKS, 256, 0, s>>>(vy, vd, nvox, part);
-  else
-    prelu_partial_kernel<float><<<PRELU_BLOCKS, 256, 0, s>>>(vy, vd, nvox, part);
+  vsrk_dispatch_dtype(y->dtype, [&](auto tag) {
+    prelu_partial_kernel<decltype(tag)><<<PRELU_BLOCKS, 256, 0, s>>>(vy, vd, nvox, part);
+  });
   VSRK_LAUNCH_CHECK("prelu_partial");
   vsrk_slope_final(part, PRELU_BLOCKS, a, da, accumulate, 0, s);
   VSRK_LAUNCH_CHECK("prelu_final");
@@ -403,12 +400,10 @@ static int prelu_bwd_impl(const vsrk_tensor5* y, const vsrk_tensor5* dy, const v
   VSRK_CHECK(((uintptr_t)workspace & 15) == 0, "prelu_bwd: workspace must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   double* part = (double*)workspace;
-  if (y->dtype == VSRK_BF16)
-    prelu_bwd_kernel<bf16><<<PRELU_BLOCKS, 256, 0, s>>>(vy, vg, vg2, dy2 != nullptr, a, vo, (int)nr64, vec, part, pre);
-  else if (y->dtype == VSRK_F16)
-    prelu_bwd_kernel<f16><<<PRELU_BLOCKS, 256, 0, s>>>(vy, vg, vg2, dy2 != nullptr, a, vo, (int)nr64, vec, part, pre);
-  else
-    prelu_bwd_kernel<float><<<PRELU_BLOCKS, 256, 0, s>>>(vy, vg, vg2, dy2 != nullptr, a, vo, (int)nr64, vec, part, pre);
+  vsrk_dispatch_dtype(y->dtype, [&](auto tag) {
+    prelu_bwd_kernel<decltype(tag)><<<PRELU_BLOCKS, 256, 0, s>>>(vy, vg, vg2, dy2 != nullptr, a, vo, (int)nr64, vec,
+                                                                 part, pre);
+  });
   VSRK_LAUNCH_CHECK("prelu_bwd");
   if (da) {  // (da == NULL: the partials stay in the workspace slot, vsrk_slope_final_sum later)
     vsrk_slope_final(part, PRELU_BLOCKS, a, da, accumulate_da, pre, s);

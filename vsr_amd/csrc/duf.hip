@@ -107,15 +107,11 @@ extern "C" int vsrk_duf_dynfilter_bwd(const float* x, const float* logits, const
   const int64_t total = (int64_t)n * h * w * upscale * upscale;
   VSRK_CHECK(total < (1ll << 31), "duf_dynfilter: too many output pixels");
   hipStream_t s = (hipStream_t)stream;
-  if (grad_dtype == VSRK_BF16)
-    launch_duf<true, bf16>(size_filter, total, s, x, logits, nullptr, nullptr, grad_out, (bf16*)grad_logits,
-                           (bf16*)grad_residual, n, h, w, upscale);
-  else if (grad_dtype == VSRK_F16)
-    launch_duf<true, f16>(size_filter, total, s, x, logits, nullptr, nullptr, grad_out, (f16*)grad_logits,
-                           (f16*)grad_residual, n, h, w, upscale);
-  else
-    launch_duf<true, float>(size_filter, total, s, x, logits, nullptr, nullptr, grad_out, (float*)grad_logits,
-                            (float*)grad_residual, n, h, w, upscale);
+  vsrk_dispatch_dtype(grad_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    launch_duf<true, T>(size_filter, total, s, x, logits, nullptr, nullptr, grad_out, (T*)grad_logits,
+                        (T*)grad_residual, n, h, w, upscale);
+  });
   VSRK_LAUNCH_CHECK("duf_dynfilter_bwd");
   return VSRK_OK;
 }

@@ -295,12 +295,9 @@ int vsrk_channel_reduce_internal(const vsrk_tensor5* x, int mode, int perm_r, fl
   const size_t need = (size_t)nblk * 2 * x->c * sizeof(float);
   VSRK_CHECK(ws && ws_bytes >= need, "channel_reduce: workspace %zu < %zu bytes", ws_bytes, need);
   float* part = (float*)ws;
-  if (x->dtype == VSRK_BF16)
-    channel_partial_kernel<bf16><<<nblk, 256, 0, s>>>(v, nv, mode, part);
-  else if (x->dtype == VSRK_F16)
-    channel_partial_kernel<f16><<<nblk, 256, 0, s>>>(v, nv, mode, part);
-  else
-    channel_partial_kernel<float><<<nblk, 256, 0, s>>>(v, nv, mode, part);
+  vsrk_dispatch_dtype(x->dtype, [&](auto tag) {
+    channel_partial_kernel<decltype(tag)><<<nblk, 256, 0, s>>>(v, nv, mode, part);
+  });
   VSRK_LAUNCH_CHECK("channel_partial");
   channel_final_kernel<<<ceil_div(x->c, 256), 256, 0, s>>>(part, nblk, x->c, mode, perm_r, scale, sum, sumsq,
                                                            accumulate);
@@ -323,21 +320,16 @@ extern "C" int vsrk_ncdhw_to_view(const float* src, int32_t n, int32_t c, int32_
                      nvox(dst) < (1ll << 31) && dhw * c < (1ll << 31);
   if (dense) {
     const int nv = (int)nvox(dst);
-    if (dst->dtype == VSRK_BF16)
-      ncdhw_to_dense_kernel<bf16><<<ceil_div(nv, 256), 256, 0, s>>>(src, c, (int)dhw, (int)cp, nv, (bf16*)dst->ptr);
-    else if (dst->dtype == VSRK_F16)
-      ncdhw_to_dense_kernel<f16><<<ceil_div(nv, 256), 256, 0, s>>>(src, c, (int)dhw, (int)cp, nv, (f16*)dst->ptr);
-    else
-      ncdhw_to_dense_kernel<float><<<ceil_div(nv, 256), 256, 0, s>>>(src, c, (int)dhw, (int)cp, nv, (float*)dst->ptr);
+    vsrk_dispatch_dtype(dst->dtype, [&](auto tag) {
+      using T = decltype(tag);
+      ncdhw_to_dense_kernel<T><<<ceil_div(nv, 256), 256, 0, s>>>(src, c, (int)dhw, (int)cp, nv, (T*)dst->ptr);
+    });
     VSRK_LAUNCH_CHECK("ncdhw_to_view(dense)");
     return VSRK_OK;
   }
-  if (dst->dtype == VSRK_BF16)
-    ncdhw_to_view_kernel<bf16><<<(int)ceil_div64(total, 256), 256, 0, s>>>(src, n, c, d, h, w, v, total);
-  else if (dst->dtype == VSRK_F16)
-    ncdhw_to_view_kernel<f16><<<(int)ceil_div64(total, 256), 256, 0, s>>>(src, n, c, d, h, w, v, total);
-  else
-    ncdhw_to_view_kernel<float><<<(int)ceil_div64(total, 256), 256, 0, s>>>(src, n, c, d, h, w, v, total);
+  vsrk_dispatch_dtype(dst->dtype, [&](auto tag) {
+    ncdhw_to_view_kernel<decltype(tag)><<<(int)ceil_div64(total, 256), 256, 0, s>>>(src, n, c, d, h, w, v, total);
+  });
   VSRK_LAUNCH_CHECK("ncdhw_to_view");
   return VSRK_OK;
 }
@@ -348,12 +340,9 @@ extern "C" int vsrk_view_to_ncdhw(const vsrk_tensor5* src, float* dst, int32_t c
   View v = make_view(src);
   const int64_t total = nvox(src) * c;
   hipStream_t s = (hipStream_t)stream;
-  if (src->dtype == VSRK_BF16)
-    view_to_ncdhw_kernel<bf16><<<(int)ceil_div64(total, 256), 256, 0, s>>>(v, dst, c, total);
-  else if (src->dtype == VSRK_F16)
-    view_to_ncdhw_kernel<f16><<<(int)ceil_div64(total, 256), 256, 0, s>>>(v, dst, c, total);
-  else
-    view_to_ncdhw_kernel<float><<<(int)ceil_div64(total, 256), 256, 0, s>>>(v, dst, c, total);
+  vsrk_dispatch_dtype(src->dtype, [&](auto tag) {
+    view_to_ncdhw_kernel<decltype(tag)><<<(int)ceil_div64(total, 256), 256, 0, s>>>(v, dst, c, total);
+  });
   VSRK_LAUNCH_CHECK("view_to_ncdhw");
   return VSRK_OK;
 }
@@ -363,12 +352,10 @@ extern "C" int vsrk_relu_bwd(const vsrk_tensor5* y, const vsrk_tensor5* dy, cons
   VSRK_CHECK(y->dtype == dy->dtype && y->dtype == dx->dtype, "relu_bwd: dtype mismatch");
   const int64_t total = nvox(y) * y->c;
   hipStream_t s = (hipStream_t)stream;
-  if (y->dtype == VSRK_BF16)
-    relu_bwd_kernel<bf16><<<(int)ceil_div64(total, 256), 256, 0, s>>>(make_view(y), make_view(dy), make_view(dx), total);
-  else if (y->dtype == VSRK_F16)
-    relu_bwd_kernel<f16><<<(int)ceil_div64(total, 256), 256, 0, s>>>(make_view(y), make_view(dy), make_view(dx), total);
-  else
-    relu_bwd_kernel<float><<<(int)ceil_div64(total, 256), 256, 0, s>>>(make_view(y), make_view(dy), make_view(dx), total);
+  vsrk_dispatch_dtype(y->dtype, [&](auto tag) {
+    relu_bwd_kernel<decltype(tag)><<<(int)ceil_div64(total, 256), 256, 0, s>>>(make_view(y), make_view(dy),
+                                                                               make_view(dx), total);
+  });
   VSRK_LAUNCH_CHECK("relu_bwd");
   return VSRK_OK;
 }
@@ -378,12 +365,10 @@ extern "C" int vsrk_add(const vsrk_tensor5* a, const vsrk_tensor5* b, const vsrk
   VSRK_CHECK(a->dtype == b->dtype && a->dtype == out->dtype, "add: dtype mismatch");
   const int64_t total = nvox(a) * a->c;
   hipStream_t s = (hipStream_t)stream;
-  if (a->dtype == VSRK_BF16)
-    add_kernel<bf16><<<(int)ceil_div64(total, 256), 256, 0, s>>>(make_view(a), make_view(b), make_view(out), total);
-  else if (a->dtype == VSRK_F16)
-    add_kernel<f16><<<(int)ceil_div64(total, 256), 256, 0, s>>>(make_view(a), make_view(b), make_view(out), total);
-  else
-    add_kernel<float><<<(int)ceil_div64(total, 256), 256, 0, s>>>(make_view(a), make_view(b), make_view(out), total);
+  vsrk_dispatch_dtype(a->dtype, [&](auto tag) {
+    add_kernel<decltype(tag)><<<(int)ceil_div64(total, 256), 256, 0, s>>>(make_view(a), make_view(b), make_view(out),
+                                                                          total);
+  });
   VSRK_LAUNCH_CHECK("add");
   return VSRK_OK;
 }
@@ -405,12 +390,9 @@ static int launch_tanh(const char* name, const vsrk_tensor5* a, const vsrk_tenso
              (long long)total);
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)ceil_div64(total, 256));
-  if (a->dtype == VSRK_BF16)
-    tanh_kernel<bf16, BWD><<<grid, 256, 0, s>>>(make_view(a), make_view(b), make_view(o), total);
-  else if (a->dtype == VSRK_F16)
-    tanh_kernel<f16, BWD><<<grid, 256, 0, s>>>(make_view(a), make_view(b), make_view(o), total);
-  else
-    tanh_kernel<float, BWD><<<grid, 256, 0, s>>>(make_view(a), make_view(b), make_view(o), total);
+  vsrk_dispatch_dtype(a->dtype, [&](auto tag) {
+    tanh_kernel<decltype(tag), BWD><<<grid, 256, 0, s>>>(make_view(a), make_view(b), make_view(o), total);
+  });
   VSRK_LAUNCH_CHECK(name);
   return VSRK_OK;
 }
@@ -444,12 +426,10 @@ extern "C" int vsrk_loss_bwd(int32_t kind, float param, const float* out, const 
   VSRK_CHECK(out && target && grad, "loss_bwd: null argument");
   const int nblk = (int)std::min<int64_t>(4096, std::max<int64_t>(1, ceil_div64(count, 256)));
   hipStream_t s = (hipStream_t)stream;
-  if (grad_dtype == VSRK_BF16)
-    loss_bwd_kernel<bf16><<<nblk, 256, 0, s>>>(kind, param, out, target, count, gscale, (bf16*)grad);
-  else if (grad_dtype == VSRK_F16)
-    loss_bwd_kernel<f16><<<nblk, 256, 0, s>>>(kind, param, out, target, count, gscale, (f16*)grad);
-  else
-    loss_bwd_kernel<float><<<nblk, 256, 0, s>>>(kind, param, out, target, count, gscale, (float*)grad);
+  vsrk_dispatch_dtype(grad_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    loss_bwd_kernel<T><<<nblk, 256, 0, s>>>(kind, param, out, target, count, gscale, (T*)grad);
+  });
   VSRK_LAUNCH_CHECK("loss_bwd");
   return VSRK_OK;
 }

@@ -158,23 +158,11 @@ __global__ __launch_bounds__(256) void upsample_cl_bwd_kernel(View gy, View gx, 
   Lane<T, VEC>::store(xp, acc);
 }
 
-int check_view(const char* name, const vsrk_tensor5* t) {
-  VSRK_CHECK(t && t->ptr, "%s: null argument", name);
-  VSRK_CHECK(t->dtype == VSRK_F32 || t->dtype == VSRK_BF16 || t->dtype == VSRK_F16, "%s: unknown dtype %d", name,
-             t->dtype);
-  VSRK_CHECK(t->shuffle <= 1, "%s: plain views only", name);
-  VSRK_CHECK(t->n >= 1 && t->d == 1 && t->c >= 1 && t->h >= 0 && t->w >= 0, "%s: view (%d, %d, %d, %d, %d) must be "
-             "(n, 1, h, w, c)", name, t->n, t->d, t->h, t->w, t->c);
-  return VSRK_OK;
-}
-
 // `small` is the (h, w) side and `big` the (f h [+ 1], f w [+ 1]) side of a pool (f = 2, odd sizes floor) or
 // an upsampling (exact)
 int check_pair(const char* name, const vsrk_tensor5* small, const vsrk_tensor5* big, int f, bool floor_ok) {
-  int rc = check_view(name, small);
-  if (rc != VSRK_OK) return rc;
-  rc = check_view(name, big);
-  if (rc != VSRK_OK) return rc;
+  VSRK_TRY(check_view(name, small, false));
+  VSRK_TRY(check_view(name, big, false));
   VSRK_CHECK(small->dtype == big->dtype, "%s: dtype mismatch (%d and %d)", name, small->dtype, big->dtype);
   VSRK_CHECK(small->n == big->n && small->c == big->c, "%s: batch / channel mismatch (%d, %d) and (%d, %d)", name,
              small->n, small->c, big->n, big->c);
@@ -192,28 +180,30 @@ int check_pair(const char* name, const vsrk_tensor5* small, const vsrk_tensor5* 
 }  // namespace
 
 extern "C" int vsrk_max_pool2x2_fwd(const vsrk_tensor5* x, const vsrk_tensor5* y, void* stream) {
-  const int rc = check_pair("max_pool2x2_fwd", y, x, 2, true);
-  if (rc != VSRK_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
+  VSRK_TRY(check_pair("max_pool2x2_fwd", y, x, 2, true));
   const bool vec = vec_ok(x) && vec_ok(y);
-  VSRK_CL_LAUNCH(max_pool2x2_fwd_kernel, x->dtype, vec, (int64_t)y->n * y->h * y->w, y->c, make_view(x), make_view(y));
+  const int nc = chunks(x->dtype, vec, y->c);
+  const int64_t total = (int64_t)y->n * y->h * y->w * nc;
+  launch_lanes(x->dtype, vec, total, stream, [&](auto lane, dim3 grid, hipStream_t s) {
+    using L = decltype(lane);
+    max_pool2x2_fwd_kernel<typename L::Elem, L::Vec><<<grid, 256, 0, s>>>(make_view(x), make_view(y), nc, total);
+  });
   VSRK_LAUNCH_CHECK("max_pool2x2_fwd");
   return VSRK_OK;
 }
 
 extern "C" int vsrk_max_pool2x2_bwd(const vsrk_tensor5* x, const vsrk_tensor5* gy, const vsrk_tensor5* gx,
                                     void* stream) {
-  int rc = check_pair("max_pool2x2_bwd", gy, x, 2, true);
-  if (rc != VSRK_OK) return rc;
-  rc = check_view("max_pool2x2_bwd", gx);
-  if (rc != VSRK_OK) return rc;
-  VSRK_CHECK(gx->dtype == x->dtype && gx->n == x->n && gx->h == x->h && gx->w == x->w && gx->c == x->c,
-             "max_pool2x2_bwd: gx (%d, %d, %d, %d) does not match x (%d, %d, %d, %d)", gx->n, gx->h, gx->w, gx->c, x->n,
-             x->h, x->w, x->c);
-  hipStream_t s = (hipStream_t)stream;
+  VSRK_TRY(check_pair("max_pool2x2_bwd", gy, x, 2, true));
+  VSRK_TRY(check_shape("max_pool2x2_bwd", "gx", gx, x->dtype, x->n, x->h, x->w, x->c, false));
   const bool vec = vec_ok(x) && vec_ok(gy) && vec_ok(gx);
-  VSRK_CL_LAUNCH(max_pool2x2_bwd_kernel, x->dtype, vec, (int64_t)x->n * x->h * x->w, x->c, make_view(x), make_view(gy),
-                 make_view(gx));
+  const int nc = chunks(x->dtype, vec, x->c);
+  const int64_t total = (int64_t)x->n * x->h * x->w * nc;
+  launch_lanes(x->dtype, vec, total, stream, [&](auto lane, dim3 grid, hipStream_t s) {
+    using L = decltype(lane);
+    max_pool2x2_bwd_kernel<typename L::Elem, L::Vec><<<grid, 256, 0, s>>>(make_view(x), make_view(gy), make_view(gx),
+                                                                          nc, total);
+  });
   VSRK_LAUNCH_CHECK("max_pool2x2_bwd");
   return VSRK_OK;
 }
@@ -229,24 +219,30 @@ static int check_up(const char* name, const vsrk_tensor5* small, const vsrk_tens
 
 extern "C" int vsrk_upsample_cl_fwd(const vsrk_tensor5* x, const vsrk_tensor5* y, int32_t r, int32_t align_corners,
                                     int32_t accumulate, void* stream) {
-  const int rc = check_up("upsample_cl_fwd", x, y, r, align_corners, accumulate);
-  if (rc != VSRK_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
+  VSRK_TRY(check_up("upsample_cl_fwd", x, y, r, align_corners, accumulate));
   const bool vec = vec_ok(x) && vec_ok(y);
-  VSRK_CL_LAUNCH(upsample_cl_fwd_kernel, x->dtype, vec, (int64_t)y->n * y->h * y->w, y->c, make_view(x), make_view(y),
-                 r, align_corners, accumulate);
+  const int nc = chunks(x->dtype, vec, y->c);
+  const int64_t total = (int64_t)y->n * y->h * y->w * nc;
+  launch_lanes(x->dtype, vec, total, stream, [&](auto lane, dim3 grid, hipStream_t s) {
+    using L = decltype(lane);
+    upsample_cl_fwd_kernel<typename L::Elem, L::Vec><<<grid, 256, 0, s>>>(make_view(x), make_view(y), r, align_corners,
+                                                                          accumulate, nc, total);
+  });
   VSRK_LAUNCH_CHECK("upsample_cl_fwd");
   return VSRK_OK;
 }
 
 extern "C" int vsrk_upsample_cl_bwd(const vsrk_tensor5* gy, const vsrk_tensor5* gx, int32_t r, int32_t align_corners,
                                     int32_t accumulate, void* stream) {
-  const int rc = check_up("upsample_cl_bwd", gx, gy, r, align_corners, accumulate);
-  if (rc != VSRK_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
+  VSRK_TRY(check_up("upsample_cl_bwd", gx, gy, r, align_corners, accumulate));
   const bool vec = vec_ok(gx) && vec_ok(gy);
-  VSRK_CL_LAUNCH(upsample_cl_bwd_kernel, gx->dtype, vec, (int64_t)gx->n * gx->h * gx->w, gx->c, make_view(gy),
-                 make_view(gx), r, align_corners, accumulate);
+  const int nc = chunks(gx->dtype, vec, gx->c);
+  const int64_t total = (int64_t)gx->n * gx->h * gx->w * nc;
+  launch_lanes(gx->dtype, vec, total, stream, [&](auto lane, dim3 grid, hipStream_t s) {
+    using L = decltype(lane);
+    upsample_cl_bwd_kernel<typename L::Elem, L::Vec><<<grid, 256, 0, s>>>(make_view(gy), make_view(gx), r,
+                                                                          align_corners, accumulate, nc, total);
+  });
   VSRK_LAUNCH_CHECK("upsample_cl_bwd");
   return VSRK_OK;
 }

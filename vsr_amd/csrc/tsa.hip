@@ -263,60 +263,20 @@ __global__ __launch_bounds__(256) void modulate_bwd_kernel(View fea, View att, V
 }
 
 // ---- argument checks ----
-int check_view(const char* name, const vsrk_tensor5* t) {
-  VSRK_CHECK(t && t->ptr, "%s: null argument", name);
-  VSRK_CHECK(t->dtype == VSRK_F32 || t->dtype == VSRK_BF16 || t->dtype == VSRK_F16, "%s: unknown dtype %d", name,
-             t->dtype);
-  VSRK_CHECK(t->shuffle <= 1, "%s: plain views only", name);
-  VSRK_CHECK(t->n >= 1 && t->d == 1 && t->h >= 1 && t->w >= 1 && t->c >= 1,
-             "%s: view (%d, %d, %d, %d, %d) must be (n, 1, h, w, c), not empty", name, t->n, t->d, t->h, t->w, t->c);
-  // one lane per chunk in 256-thread workgroups: the grid is a 32-bit count
-  VSRK_CHECK((int64_t)t->n * t->h * t->w * t->c <= ((int64_t)1 << 39), "%s: tensor too large", name);
-  return VSRK_OK;
-}
-
 // `t` is a view of `like`'s dtype and (n, h, w) with c channels
 int check_like(const char* name, const char* what, const vsrk_tensor5* t, const vsrk_tensor5* like, int n, int c) {
-  const int rc = check_view(name, t);
-  if (rc != VSRK_OK) return rc;
-  VSRK_CHECK(t->dtype == like->dtype, "%s: %s dtype mismatch (%d and %d)", name, what, t->dtype, like->dtype);
-  VSRK_CHECK(t->n == n && t->h == like->h && t->w == like->w && t->c == c,
-             "%s: %s is (%d, 1, %d, %d, %d), expected (%d, 1, %d, %d, %d)", name, what, t->n, t->h, t->w, t->c, n,
-             like->h, like->w, c);
-  return VSRK_OK;
+  return check_shape(name, what, t, like->dtype, n, like->h, like->w, c);
 }
-
-#define VSRK_TRY(expr)             \
-  do {                             \
-    const int rc_ = (expr);        \
-    if (rc_ != VSRK_OK) return rc_; \
-  } while (0)
 
 // lanes per pixel of the attention kernels: log2 of the power of two >= nc
 int tatt_lshift(const char* name, int c, bool vec, int dtype, int& nc, int& lshift) {
-  const int E = vec ? 16 / vsrk_esize(dtype) : 1;
-  nc = c / E;
+  nc = chunks(dtype, vec, c);
   VSRK_CHECK(nc <= 64, "%s: %d channels%s need more than the 64 lanes of a wavefront", name, c,
              vec ? "" : " (views that do not allow 16-byte accesses)");
   lshift = 0;
   while ((1 << lshift) < nc) ++lshift;
   return VSRK_OK;
 }
-
-#define VSRK_TATT_LAUNCH(KERNEL, dtype, vec, threads, arg)                      \
-  do {                                                                          \
-    const dim3 grid((unsigned)ceil_div64(threads, 256));                        \
-    if ((dtype) == VSRK_BF16) {                                                 \
-      if (vec) KERNEL<bf16, true><<<grid, 256, 0, s>>>(arg);                    \
-      else KERNEL<bf16, false><<<grid, 256, 0, s>>>(arg);                       \
-    } else if ((dtype) == VSRK_F16) {                                           \
-      if (vec) KERNEL<f16, true><<<grid, 256, 0, s>>>(arg);                     \
-      else KERNEL<f16, false><<<grid, 256, 0, s>>>(arg);                        \
-    } else {                                                                    \
-      if (vec) KERNEL<float, true><<<grid, 256, 0, s>>>(arg);                   \
-      else KERNEL<float, false><<<grid, 256, 0, s>>>(arg);                      \
-    }                                                                           \
-  } while (0)
 
 int check_tatt(const char* name, const vsrk_tensor5* emb, const vsrk_tensor5* ref, const vsrk_tensor5* al,
                const vsrk_tensor5* out, int& nframes) {
@@ -353,10 +313,12 @@ extern "C" int vsrk_tsa_tatt_fwd(const vsrk_tensor5* emb, const vsrk_tensor5* em
   // out's channel slices start at multiples of c: 16-byte aligned when c is a multiple of the chunk
   const bool vec = vec_ok(emb) && vec_ok(emb_ref) && vec_ok(aligned) && vec_ok(out);
   VSRK_TRY(tatt_lshift("tsa_tatt_fwd", emb->c, vec, emb->dtype, nc, lshift));
-  hipStream_t s = (hipStream_t)stream;
   TattFwd a = {make_view(emb), make_view(emb_ref), make_view(aligned), make_view(out), prob, nframes, nc, lshift,
                (int64_t)emb->n * emb->h * emb->w};
-  VSRK_TATT_LAUNCH(tatt_fwd_kernel, emb->dtype, vec, a.groups << lshift, a);
+  launch_lanes(emb->dtype, vec, a.groups << lshift, stream, [&](auto lane, dim3 grid, hipStream_t s) {
+    using L = decltype(lane);
+    tatt_fwd_kernel<typename L::Elem, L::Vec><<<grid, 256, 0, s>>>(a);
+  });
   VSRK_LAUNCH_CHECK("tsa_tatt_fwd");
   return VSRK_OK;
 }
@@ -374,20 +336,26 @@ extern "C" int vsrk_tsa_tatt_bwd(const vsrk_tensor5* emb, const vsrk_tensor5* em
   const bool vec = vec_ok(emb) && vec_ok(emb_ref) && vec_ok(aligned) && vec_ok(gout) && vec_ok(g_emb) &&
                    vec_ok(g_emb_ref) && vec_ok(g_aligned);
   VSRK_TRY(tatt_lshift(name, emb->c, vec, emb->dtype, nc, lshift));
-  hipStream_t s = (hipStream_t)stream;
   TattBwd a = {make_view(emb), make_view(emb_ref), make_view(aligned), make_view(gout), make_view(g_emb),
                make_view(g_emb_ref), make_view(g_aligned), prob, nframes, nc, lshift,
                (int64_t)emb_ref->n * emb->h * emb->w};
-  VSRK_TATT_LAUNCH(tatt_bwd_kernel, emb->dtype, vec, a.groups << lshift, a);
+  launch_lanes(emb->dtype, vec, a.groups << lshift, stream, [&](auto lane, dim3 grid, hipStream_t s) {
+    using L = decltype(lane);
+    tatt_bwd_kernel<typename L::Elem, L::Vec><<<grid, 256, 0, s>>>(a);
+  });
   VSRK_LAUNCH_CHECK(name);
   return VSRK_OK;
 }
 
 extern "C" int vsrk_pool3s2_fwd(const vsrk_tensor5* x, const vsrk_tensor5* y, void* stream) {
   VSRK_TRY(check_pool("pool3s2_fwd", x, y));
-  hipStream_t s = (hipStream_t)stream;
   const bool vec = vec_ok(x) && vec_ok(y);
-  VSRK_CL_LAUNCH(pool3s2_fwd_kernel, x->dtype, vec, (int64_t)y->n * y->h * y->w, x->c, make_view(x), make_view(y));
+  const int nc = chunks(x->dtype, vec, x->c);
+  const int64_t total = (int64_t)y->n * y->h * y->w * nc;
+  launch_lanes(x->dtype, vec, total, stream, [&](auto lane, dim3 grid, hipStream_t s) {
+    using L = decltype(lane);
+    pool3s2_fwd_kernel<typename L::Elem, L::Vec><<<grid, 256, 0, s>>>(make_view(x), make_view(y), nc, total);
+  });
   VSRK_LAUNCH_CHECK("pool3s2_fwd");
   return VSRK_OK;
 }
@@ -395,10 +363,14 @@ extern "C" int vsrk_pool3s2_fwd(const vsrk_tensor5* x, const vsrk_tensor5* y, vo
 extern "C" int vsrk_pool3s2_bwd(const vsrk_tensor5* x, const vsrk_tensor5* gy, const vsrk_tensor5* gx, void* stream) {
   VSRK_TRY(check_pool("pool3s2_bwd", x, gy));
   VSRK_TRY(check_like("pool3s2_bwd", "gx", gx, x, x->n, x->c));
-  hipStream_t s = (hipStream_t)stream;
   const bool vec = vec_ok(x) && vec_ok(gy) && vec_ok(gx);
-  VSRK_CL_LAUNCH(pool3s2_bwd_kernel, x->dtype, vec, (int64_t)x->n * x->h * x->w, x->c, make_view(x), make_view(gy),
-                 make_view(gx));
+  const int nc = chunks(x->dtype, vec, x->c);
+  const int64_t total = (int64_t)x->n * x->h * x->w * nc;
+  launch_lanes(x->dtype, vec, total, stream, [&](auto lane, dim3 grid, hipStream_t s) {
+    using L = decltype(lane);
+    pool3s2_bwd_kernel<typename L::Elem, L::Vec><<<grid, 256, 0, s>>>(make_view(x), make_view(gy), make_view(gx), nc,
+                                                                      total);
+  });
   VSRK_LAUNCH_CHECK("pool3s2_bwd");
   return VSRK_OK;
 }
@@ -410,10 +382,14 @@ extern "C" int vsrk_tsa_modulate_fwd(const vsrk_tensor5* fea, const vsrk_tensor5
   VSRK_TRY(check_like(name, "att", att, fea, fea->n, fea->c));
   VSRK_TRY(check_like(name, "att_add", att_add, fea, fea->n, fea->c));
   VSRK_TRY(check_like(name, "out", out, fea, fea->n, fea->c));
-  hipStream_t s = (hipStream_t)stream;
   const bool vec = vec_ok(fea) && vec_ok(att) && vec_ok(att_add) && vec_ok(out);
-  VSRK_CL_LAUNCH(modulate_fwd_kernel, fea->dtype, vec, (int64_t)fea->n * fea->h * fea->w, fea->c, make_view(fea),
-                 make_view(att), make_view(att_add), make_view(out));
+  const int nc = chunks(fea->dtype, vec, fea->c);
+  const int64_t total = (int64_t)fea->n * fea->h * fea->w * nc;
+  launch_lanes(fea->dtype, vec, total, stream, [&](auto lane, dim3 grid, hipStream_t s) {
+    using L = decltype(lane);
+    modulate_fwd_kernel<typename L::Elem, L::Vec><<<grid, 256, 0, s>>>(make_view(fea), make_view(att),
+                                                                       make_view(att_add), make_view(out), nc, total);
+  });
   VSRK_LAUNCH_CHECK(name);
   return VSRK_OK;
 }
@@ -428,12 +404,16 @@ extern "C" int vsrk_tsa_modulate_bwd(const vsrk_tensor5* fea, const vsrk_tensor5
   VSRK_TRY(check_like(name, "gfea", gfea, fea, fea->n, fea->c));
   VSRK_TRY(check_like(name, "gatt", gatt, fea, fea->n, fea->c));
   if (gatt_add) VSRK_TRY(check_like(name, "gatt_add", gatt_add, fea, fea->n, fea->c));
-  hipStream_t s = (hipStream_t)stream;
   const bool vec = vec_ok(fea) && vec_ok(att) && vec_ok(g) && vec_ok(gfea) && vec_ok(gatt) &&
                    (!gatt_add || vec_ok(gatt_add));
-  VSRK_CL_LAUNCH(modulate_bwd_kernel, fea->dtype, vec, (int64_t)fea->n * fea->h * fea->w, fea->c, make_view(fea),
-                 make_view(att), make_view(g), make_view(gfea), make_view(gatt), make_view(gatt_add ? gatt_add : g),
-                 gatt_add ? 1 : 0);
+  const int nc = chunks(fea->dtype, vec, fea->c);
+  const int64_t total = (int64_t)fea->n * fea->h * fea->w * nc;
+  launch_lanes(fea->dtype, vec, total, stream, [&](auto lane, dim3 grid, hipStream_t s) {
+    using L = decltype(lane);
+    modulate_bwd_kernel<typename L::Elem, L::Vec><<<grid, 256, 0, s>>>(
+        make_view(fea), make_view(att), make_view(g), make_view(gfea), make_view(gatt),
+        make_view(gatt_add ? gatt_add : g), gatt_add ? 1 : 0, nc, total);
+  });
   VSRK_LAUNCH_CHECK(name);
   return VSRK_OK;
 }

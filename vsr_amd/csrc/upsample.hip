@@ -176,12 +176,9 @@ extern "C" int vsrk_upsample2d_fwd(int32_t dtype, const void* x, int64_t planes,
   const int rc = check_args("upsample2d_fwd", dtype, x, y, planes, h, w, r, mode, align_corners, accumulate);
   if (rc != VSRK_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == VSRK_BF16)
-    launch_fwd<bf16>(x, y, planes, h, w, r, mode, align_corners, accumulate, s);
-  else if (dtype == VSRK_F16)
-    launch_fwd<f16>(x, y, planes, h, w, r, mode, align_corners, accumulate, s);
-  else
-    launch_fwd<float>(x, y, planes, h, w, r, mode, align_corners, accumulate, s);
+  vsrk_dispatch_dtype(dtype, [&](auto tag) {
+    launch_fwd<decltype(tag)>(x, y, planes, h, w, r, mode, align_corners, accumulate, s);
+  });
   VSRK_LAUNCH_CHECK("upsample2d_fwd");
   return VSRK_OK;
 }
@@ -191,12 +188,9 @@ extern "C" int vsrk_upsample2d_bwd(int32_t dtype, const void* gy, int64_t planes
   const int rc = check_args("upsample2d_bwd", dtype, gy, gx, planes, h, w, r, mode, align_corners, accumulate);
   if (rc != VSRK_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == VSRK_BF16)
-    launch_bwd<bf16>(gy, gx, planes, h, w, r, mode, align_corners, accumulate, s);
-  else if (dtype == VSRK_F16)
-    launch_bwd<f16>(gy, gx, planes, h, w, r, mode, align_corners, accumulate, s);
-  else
-    launch_bwd<float>(gy, gx, planes, h, w, r, mode, align_corners, accumulate, s);
+  vsrk_dispatch_dtype(dtype, [&](auto tag) {
+    launch_bwd<decltype(tag)>(gy, gx, planes, h, w, r, mode, align_corners, accumulate, s);
+  });
   VSRK_LAUNCH_CHECK("upsample2d_bwd");
   return VSRK_OK;
 }

@@ -144,3 +144,10 @@ static inline auto vsrk_dispatch16(int dt, Fn&& f) {
   if (dt == VSRK_F16) return f(f16{});
   return f(bf16{});
 }
+// Call f(tag) with a value of the element type of dtype dt: bf16, f16, or float for anything else.
+template <typename Fn>
+static inline auto vsrk_dispatch_dtype(int dt, Fn&& f) {
+  if (dt == VSRK_BF16) return f(bf16{});
+  if (dt == VSRK_F16) return f(f16{});
+  return f(float{});
+}

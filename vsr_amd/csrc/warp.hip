@@ -242,12 +242,9 @@ extern "C" int vsrk_flow_warp_fwd(const vsrk_tensor5* img, const float* flow, in
   const dim3 grid((unsigned)ceil_div64(total, 256));
   const View iv = make_view(img), ov = make_view(out);
   const WarpCfg cfg = {s2d, padding_mode, align_corners, flow_up, mesh_step(img->w), mesh_step(img->h)};
-  if (img->dtype == VSRK_BF16)
-    flow_warp_fwd_kernel<bf16><<<grid, 256, 0, s>>>(iv, flow, ov, cfg, total);
-  else if (img->dtype == VSRK_F16)
-    flow_warp_fwd_kernel<f16><<<grid, 256, 0, s>>>(iv, flow, ov, cfg, total);
-  else
-    flow_warp_fwd_kernel<float><<<grid, 256, 0, s>>>(iv, flow, ov, cfg, total);
+  vsrk_dispatch_dtype(img->dtype, [&](auto tag) {
+    flow_warp_fwd_kernel<decltype(tag)><<<grid, 256, 0, s>>>(iv, flow, ov, cfg, total);
+  });
   VSRK_LAUNCH_CHECK("flow_warp_fwd");
   return VSRK_OK;
 }
@@ -264,12 +261,9 @@ extern "C" int vsrk_flow_warp_bwd(const vsrk_tensor5* img, const float* flow, in
   const dim3 grid((unsigned)ceil_div64(total, 256));
   const View iv = make_view(img), gv = make_view(gout);
   const WarpCfg cfg = {s2d, padding_mode, align_corners, flow_up, mesh_step(img->w), mesh_step(img->h)};
-  if (img->dtype == VSRK_BF16)
-    flow_warp_bwd_kernel<bf16><<<grid, 256, 0, s>>>(iv, flow, gv, cfg, accumulate, gflow, total);
-  else if (img->dtype == VSRK_F16)
-    flow_warp_bwd_kernel<f16><<<grid, 256, 0, s>>>(iv, flow, gv, cfg, accumulate, gflow, total);
-  else
-    flow_warp_bwd_kernel<float><<<grid, 256, 0, s>>>(iv, flow, gv, cfg, accumulate, gflow, total);
+  vsrk_dispatch_dtype(img->dtype, [&](auto tag) {
+    flow_warp_bwd_kernel<decltype(tag)><<<grid, 256, 0, s>>>(iv, flow, gv, cfg, accumulate, gflow, total);
+  });
   VSRK_LAUNCH_CHECK("flow_warp_bwd");
   return VSRK_OK;
 }

@@ -21,7 +21,6 @@ kernels).
 """
 from __future__ import annotations
 
-import ctypes as C
 import logging
 import math
 
@@ -37,17 +36,6 @@ logger = logging.getLogger(__name__)
 K1, P0 = (1, 1, 1), (0, 0, 0)
 
 
-def _geometry(x, weight, stride, padding, dilation, dg):
-    n, c, h, w = x.shape
-    kh, kw = weight.shape[2:]
-    sh, sw = stride
-    ph, pw = padding
-    dh, dw = dilation
-    ho = (h + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1
-    wo = (w + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1
-    return (C.c_int32 * 15)(n, h, w, c, ho, wo, kh, kw, sh, sw, ph, pw, dh, dw, dg), ho, wo
-
-
 class _DcnFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, offset, mask, weight, bias, stride, padding, dilation, groups, dg):
@@ -58,13 +46,13 @@ class _DcnFunction(torch.autograd.Function):
         x, offset = x.float().contiguous(), offset.float().contiguous()
         mask = mask.float().contiguous() if mask is not None else None
         lib = N.load()
-        geo, ho, wo = _geometry(x, weight, stride, padding, dilation, dg)
+        xcl = x.permute(0, 2, 3, 1).contiguous()
+        geo, ho, wo = F.dcn_geometry(xcl.unsqueeze(1), weight.shape[2:], stride, padding, dilation, dg)
         n, c = x.shape[:2]
         co, _, kh, kw = weight.shape
         K = kh * kw
         if offset.shape != (n, dg * 2 * K, ho, wo) or (mask is not None and mask.shape != (n, dg * K, ho, wo)):
             raise ValueError("offset / mask shape does not match the conv geometry")
-        xcl = x.permute(0, 2, 3, 1).contiguous()
         cols = torch.empty((n, 1, ho, wo, K * c), dtype=torch.float32, device=x.device)
         sp = N.stream_ptr(x.device)
         N.check(lib.vsrk_dcn_im2col(geo, xcl.data_ptr(), offset.data_ptr(), N.ptr(mask), cols.data_ptr(), sp),
