@@ -369,3 +369,57 @@ def test_pw_fused_reduce_bnb(c, alias, hw, grid_cap):
     err = (outs[0] - ref).abs().max().item()
     assert err <= 1e-5 * (1 + ref.abs().max().item()), err
     assert torch.equal(outs[0], outs[1])
+
+
+@pytest.mark.parametrize("form,ci,co", [("bias", 64, 60), ("bias", 128, 124), ("mask+acc", 64, 60),
+                                        ("relu-mask+acc", 64, 64), ("relu-mask+acc", 256, 256),
+                                        ("prologue-mask", 64, 64), ("prologue-prelu", 64, 64)])
+def test_pw_forms_the_staged_kernel_declines(form, ci, co, grid_cap):
+    """Pointwise shapes whose form the staged kernel does not have (an output
+    that is not a whole number of 8-channel chunks; a mask or accumulate
+    operand together with a prologue or an activation; a prologue with PReLU):
+    correct against fp64 by whichever conv kernel serves them.  190 voxels: a
+    voxel tail at every tile size; channel-slice input and output views, the
+    rest of the output buffer untouched."""
+    g = torch.Generator().manual_seed(11 * ci + co + len(form))
+    n, d, h, w = 2, 1, 5, 19
+    big = torch.randn((n, d, h, w, ci + 32), generator=g)
+    wt = torch.randn((co, ci), generator=g) / ci ** 0.5
+    b = torch.randn(co, generator=g)
+    sc = torch.rand(ci, generator=g) + 0.5
+    sh = torch.randn(ci, generator=g)
+    mask = torch.randn((n, d, h, w, co), generator=g)
+    y0 = torch.randn((n, d, h, w, co + 64), generator=g)
+    slope = torch.tensor([0.2])
+    xin = _q(big[..., 16:16 + ci])
+    pro = dict(prologue=F.PRO_AFFINE_RELU, pro_scale=sc.to(DEV), pro_shift=sh.to(DEV))
+    if form.startswith("prologue"):
+        xin = torch.relu(xin * sc.double() + sh.double()).to(BF).double()
+    ref = torch.einsum("ndhwc,oc->ndhwo", xin, _q(wt))
+    old = _q(y0[..., 32:32 + co])
+    if form == "bias":
+        ref = ref + b.double()
+        kw = dict(bias=b.to(DEV))
+    elif form == "mask+acc":
+        ref = torch.where(_q(mask) > 0, ref, torch.zeros_like(ref)) + old
+        kw = dict(mask=mask.to(DEV, BF), accumulate=True)
+    elif form == "relu-mask+acc":
+        ref = torch.where(_q(mask) > 0, torch.relu(ref), torch.zeros_like(ref)) + old
+        kw = dict(act=F.ACT_RELU, mask=mask.to(DEV, BF), accumulate=True)
+    elif form == "prologue-mask":
+        ref = torch.where(_q(mask) > 0, ref, torch.zeros_like(ref))
+        kw = dict(mask=mask.to(DEV, BF), **pro)
+    else:
+        ref = ref + b.double()
+        ref = torch.where(ref > 0, ref, 0.2 * ref)
+        kw = dict(bias=b.to(DEV), act=F.ACT_PRELU, act_param=slope.to(DEV), **pro)
+    yb = y0.to(DEV, BF)
+    F.conv(big.to(DEV, BF)[..., 16:16 + ci], F.pack_weight(wt.view(co, ci, 1, 1, 1).to(DEV), 0, BF),
+           yb[..., 32:32 + co], (1, 1, 1), (0, 0, 0), **kw)
+    y = yb[..., 32:32 + co].double().cpu()
+    err = (y - ref).abs().max().item()
+    bound = (2 if "mask" in form or "acc" in form else 1) * 1.5e-2 * ref.abs().max().item()
+    print(f"{form} {ci}->{co}: max|d| {err:.3e} bound {bound:.3e}")
+    assert err <= bound, err
+    assert torch.equal(yb[..., :32].cpu(), y0[..., :32].to(BF)) and torch.equal(yb[..., 32 + co:].cpu(),
+                                                                                 y0[..., 32 + co:].to(BF))

@@ -250,6 +250,30 @@ __device__ __forceinline__ v4i16 ds_read_tr(const char* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(p));
 }
 
+// Raw buffer access of the pointwise kernels (conv_pw_impl.h, conv_pw_wide.hip),
+// in a namespace of its own: a kernel file opts in with a using-directive.
+namespace rawbuf {
+// Raw buffer resource over [base, base + 2 GiB) (wave-uniform base): offsets
+// at or beyond 0x7FFFFFF0 read as zero and drop stores -- the out-of-range
+// voxels and channels of a tile, without branches.
+typedef __amdgpu_buffer_rsrc_t Rsrc;
+constexpr uint32_t OOB = 0x80000000u;
+__device__ __forceinline__ Rsrc rsrc_at(const void* base) {
+  const uint64_t b = (uint64_t)base;
+  const uint64_t u = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32)) << 32) |
+                     (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
+  return __builtin_amdgcn_make_buffer_rsrc((void*)u, 0, 0x7FFFFFF0, 0x00020000);
+}
+typedef int v4i_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint4 bload16(Rsrc r, uint32_t off) {
+  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
+}
+template <int AUX = 0>  // cache policy bits of the instruction (2: non-temporal)
+__device__ __forceinline__ void bstore16(Rsrc r, uint32_t off, uint4 v) {
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i_t, v), r, (int)off, 0, AUX);
+}
+}  // namespace rawbuf
+
 }  // namespace vsrk_conv
 
 

@@ -32,6 +32,9 @@ int vsrk_conv_fwd_fast(const vsrk_conv_desc* d, const vsrk_tensor5* x, const voi
   const int ye = vsrk_esize(y->dtype);
   if (((uintptr_t)y->ptr) % (4 * ye) != 0 || y->sn % 4 || y->sd % 4 || y->sh % 4 || y->sw % 4) return 0;
   if (y->c % 4 != 0 && !(y->c < 4 && !residual && !mask && !d->accumulate)) return 0;
+  // a 16-bit output is stored in whole 16-byte chunks of 8 channels (the transposed epilogue): a last
+  // chunk of 4 would run into the next channels of the buffer (the tile kernel stores it in part)
+  if (ye == 2 && y->c > 4 && y->c % 8 != 0) return 0;
   for (const vsrk_tensor5* t : {residual, mask}) {
     if (t && (((uintptr_t)t->ptr) % (4 * ye) != 0 || t->sn % 4 || t->sd % 4 || t->sh % 4 || t->sw % 4 ||
               t->shuffle > 1 || t->dtype != y->dtype))

@@ -27,6 +27,7 @@
 
 namespace {
 using namespace vsrk_conv;
+using namespace vsrk_conv::rawbuf;
 
 constexpr int WT = 512;          // 8 waves
 constexpr int WBM = 256;         // voxels per tile
@@ -35,22 +36,6 @@ constexpr int WBK = 64;          // input channels per stage
 constexpr int WRS = 2 * WBK + 16;  // LDS row stride (bytes): 144 = 36 dwords (see the layout note below)
 constexpr int WSLOT = (WBM + WBN) * WRS;  // x rows then weight rows
 constexpr int WLDS = 2 * WSLOT;            // 147456 bytes
-
-typedef int wv4i __attribute__((ext_vector_type(4)));
-typedef __amdgpu_buffer_rsrc_t WRsrc;
-constexpr uint32_t W_OOB = 0x80000000u;
-__device__ __forceinline__ WRsrc w_rsrc(const void* base) {
-  const uint64_t b = (uint64_t)base;
-  const uint64_t u = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32)) << 32) |
-                     (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
-  return __builtin_amdgcn_make_buffer_rsrc((void*)u, 0, 0x7FFFFFF0, 0x00020000);
-}
-__device__ __forceinline__ uint4 w_bload16(WRsrc r, uint32_t off) {
-  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
-}
-__device__ __forceinline__ void w_bstore16(WRsrc r, uint32_t off, uint4 v) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(wv4i, v), r, (int)off, 0, 0);
-}
 
 struct WideArgs {
   const char* x;   // voxel v at x + v * xsv (elements), channels contiguous
@@ -87,8 +72,8 @@ __global__ __launch_bounds__(WT, 1) void pw_wide_kernel(WideArgs a) {
 
   // staging roles: 512 threads x 4 pieces of 16 bytes = 256 x rows + 256 weight rows of 64 channels
   // piece p of thread t: row (t + 512 p) >> 3 ... (8 pieces per row): rows 0..255 x, 256..511 weights
-  const WRsrc rx = w_rsrc(reinterpret_cast<const H*>(a.x) + v0 * a.xsv);
-  const WRsrc rw = w_rsrc(reinterpret_cast<const H*>(a.w) + (int64_t)n0 * a.cin_pad);
+  const Rsrc rx = rsrc_at(reinterpret_cast<const H*>(a.x) + v0 * a.xsv);
+  const Rsrc rw = rsrc_at(reinterpret_cast<const H*>(a.w) + (int64_t)n0 * a.cin_pad);
   uint4 st[8];  // this thread's 8 pieces of the next stage (4 x, 4 weights)
   auto load_stage = [&](int s) __attribute__((always_inline)) {
     const int k0 = s * WBK;
@@ -97,14 +82,14 @@ __global__ __launch_bounds__(WT, 1) void pw_wide_kernel(WideArgs a) {
       const int i = tid + WT * p, row = i >> 3, pc = i & 7;
       const int c = k0 + 8 * pc;
       const bool ok = v0 + row < a.nvox && c < a.cin;
-      st[p] = w_bload16(rx, ok ? 2u * (uint32_t)(row * a.xsv + c) : W_OOB);
+      st[p] = bload16(rx, ok ? 2u * (uint32_t)(row * a.xsv + c) : OOB);
     }
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const int i = tid + WT * p, row = i >> 3, pc = i & 7;
       const int c = k0 + 8 * pc;
       const bool ok = n0 + row < a.cout_rows && c < a.cin_pad;
-      st[4 + p] = w_bload16(rw, ok ? 2u * (uint32_t)(row * a.cin_pad + c) : W_OOB);
+      st[4 + p] = bload16(rw, ok ? 2u * (uint32_t)(row * a.cin_pad + c) : OOB);
     }
   };
   auto put_stage = [&](int slot) __attribute__((always_inline)) {
@@ -166,9 +151,9 @@ __global__ __launch_bounds__(WT, 1) void pw_wide_kernel(WideArgs a) {
   // ---- epilogue ----
   const int ecc = 2 * (r >> 4) + hf;  // the lane's 8-channel chunk of a 32-channel block
   const float osc = a.out_scale;
-  const WRsrc ry = w_rsrc(reinterpret_cast<const char*>(a.y) +
+  const Rsrc ry = rsrc_at(reinterpret_cast<const char*>(a.y) +
                           v0 * a.ysv * (int64_t)(YF32 ? 4 : 2));
-  const WRsrc rm = w_rsrc(reinterpret_cast<const H*>(MASK ? a.msk : a.y) + v0 * a.msv);
+  const Rsrc rm = rsrc_at(reinterpret_cast<const H*>(MASK ? a.msk : a.y) + v0 * a.msv);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int co = n0 + wn * 128 + j * 32 + 8 * ecc;
@@ -210,33 +195,33 @@ __global__ __launch_bounds__(WT, 1) void pw_wide_kernel(WideArgs a) {
         }
         if constexpr (MASK) {
           float m[8];
-          Chunk<H>::unpack(w_bload16(rm, ok ? 2u * (uint32_t)(vt * a.msv + co) : W_OOB), m);
+          Chunk<H>::unpack(bload16(rm, ok ? 2u * (uint32_t)(vt * a.msv + co) : OOB), m);
 #pragma unroll
           for (int e = 0; e < 8; ++e) t[e] = m[e] > 0.f ? t[e] : 0.f;
         }
         if constexpr (YF32) {
-          const uint32_t off = ok ? 4u * (uint32_t)(vt * a.ysv + co) : W_OOB;
+          const uint32_t off = ok ? 4u * (uint32_t)(vt * a.ysv + co) : OOB;
           if constexpr (ACC) {
-            const uint4 o0 = w_bload16(ry, off), o1 = w_bload16(ry, ok ? off + 16u : W_OOB);
+            const uint4 o0 = bload16(ry, off), o1 = bload16(ry, ok ? off + 16u : OOB);
             t[0] += __builtin_bit_cast(float, o0.x); t[1] += __builtin_bit_cast(float, o0.y);
             t[2] += __builtin_bit_cast(float, o0.z); t[3] += __builtin_bit_cast(float, o0.w);
             t[4] += __builtin_bit_cast(float, o1.x); t[5] += __builtin_bit_cast(float, o1.y);
             t[6] += __builtin_bit_cast(float, o1.z); t[7] += __builtin_bit_cast(float, o1.w);
           }
-          w_bstore16(ry, off, make_uint4(__builtin_bit_cast(uint32_t, t[0]), __builtin_bit_cast(uint32_t, t[1]),
+          bstore16(ry, off, make_uint4(__builtin_bit_cast(uint32_t, t[0]), __builtin_bit_cast(uint32_t, t[1]),
                                           __builtin_bit_cast(uint32_t, t[2]), __builtin_bit_cast(uint32_t, t[3])));
-          w_bstore16(ry, ok ? off + 16u : W_OOB,
+          bstore16(ry, ok ? off + 16u : OOB,
                      make_uint4(__builtin_bit_cast(uint32_t, t[4]), __builtin_bit_cast(uint32_t, t[5]),
                                 __builtin_bit_cast(uint32_t, t[6]), __builtin_bit_cast(uint32_t, t[7])));
         } else {
-          const uint32_t off = ok ? 2u * (uint32_t)(vt * a.ysv + co) : W_OOB;
+          const uint32_t off = ok ? 2u * (uint32_t)(vt * a.ysv + co) : OOB;
           if constexpr (ACC) {
             float o[8];
-            Chunk<H>::unpack(w_bload16(ry, off), o);
+            Chunk<H>::unpack(bload16(ry, off), o);
 #pragma unroll
             for (int e = 0; e < 8; ++e) t[e] += o[e];
           }
-          w_bstore16(ry, off, Chunk<H>::pack(t));
+          bstore16(ry, off, Chunk<H>::pack(t));
         }
       }
     }
