@@ -43,7 +43,7 @@ enum {
 enum { VSRK_F32 = 0, VSRK_BF16 = 1, VSRK_F16 = 2 };
 
 enum { VSRK_PRO_NONE = 0, VSRK_PRO_RELU = 1, VSRK_PRO_AFFINE = 2, VSRK_PRO_AFFINE_RELU = 3 };
-enum { VSRK_ACT_NONE = 0, VSRK_ACT_RELU = 1, VSRK_ACT_PRELU = 2 };
+enum { VSRK_ACT_NONE = 0, VSRK_ACT_RELU = 1, VSRK_ACT_PRELU = 2, VSRK_ACT_PRELU_SUM = 3 };
 
 /* Channels-last view.  Element (n,d,h,w,c) lives at
  *   ptr + n*sn + d*sd + h*sh + w*sw + c                      (shuffle <= 1)
@@ -67,7 +67,13 @@ typedef struct vsrk_tensor5 {
  * out(n,do,ho,wo,co) = act(out_scale * (bias[co] + sum_{tap,ci} in(n, do+kd-pd,
  * ho+kh-ph, wo+kw-pw, ci) * W[co,ci,tap])) [* (mask > 0)] [+ residual] [+ out].
  * The input passes through the prologue first (per-channel scale/shift and/or
- * ReLU: a fused BatchNorm3d+ReLU, duf_net.py:198-203). */
+ * ReLU: a fused BatchNorm3d+ReLU, duf_net.py:198-203).
+ * act = VSRK_ACT_PRELU_SUM moves the activation behind the skip add:
+ *   out = prelu(out_scale * (bias + conv) + residual), slope *act_param
+ * -- the tail of RBPN's ResnetBlock (rbp_net.py:237-257).  residual is
+ * required; mask and accumulate are VSRK_ERR_INVALID with it.  The tile
+ * kernel (every dtype) and the 2-D rolling form (16-bit, cout % 64 == 0,
+ * plain views) implement it; every other family declines it. */
 typedef struct vsrk_conv_desc {
   int32_t kd, kh, kw;
   int32_t pd, ph, pw;
@@ -76,7 +82,7 @@ typedef struct vsrk_conv_desc {
   float out_scale;    /* multiplies (acc + bias) — EDSR res_scale (edsr_net.py:51) */
   int32_t accumulate; /* 1: out += result (gradient accumulation into concat buffers) */
   int32_t bias_perm_r; /* >1: bias is in torch pixel-shuffle order (see vsrk_conv_pack_weight perm_r) */
-  const float* act_param;  /* device scalar, VSRK_ACT_PRELU: nn.PReLU(num_parameters=1) slope (drf_net.py:56) */
+  const float* act_param;  /* device scalar, VSRK_ACT_PRELU / _PRELU_SUM: nn.PReLU(num_parameters=1) slope (drf_net.py:56) */
   const float* mask_slope; /* device scalar or NULL: where mask <= 0 the output is scaled by *mask_slope
                               instead of zeroed -- the PReLU backward dx = dy * (y > 0 ? 1 : a) */
   int32_t subpixel;   /* 0, or VSRK_SUBPIXEL(k, s, p, transposed, flipped): the weight is the
@@ -294,6 +300,12 @@ int vsrk_relu_bwd(const vsrk_tensor5* y, const vsrk_tensor5* dy, const vsrk_tens
 
 /* Sum of two views into a third (gradient merge at skip connections). */
 int vsrk_add(const vsrk_tensor5* a, const vsrk_tensor5* b, const vsrk_tensor5* out, void* stream);
+
+/* out = a - b on views of one shape and dtype (fp32 arithmetic, one output
+ * rounding): RBPN's back-projection differences l0 - x, h0 - x, h0 - h1
+ * (rbp_net.py:82,270,284) and their sign-flipped gradients.  out may alias
+ * a or b. */
+int vsrk_sub(const vsrk_tensor5* a, const vsrk_tensor5* b, const vsrk_tensor5* out, void* stream);
 
 /* Losses (fp32, mean reduction): kind 0 = L1Loss, 1 = MSELoss, 2 = HuberLoss
  * (losses.py:5-20, param = delta), 3 = CharbonnierLoss (losses.py:23-34,

@@ -19,7 +19,7 @@ VSRK_F32 = 0
 VSRK_BF16 = 1
 VSRK_F16 = 2
 PRO_NONE, PRO_RELU, PRO_AFFINE, PRO_AFFINE_RELU = 0, 1, 2, 3
-ACT_NONE, ACT_RELU, ACT_PRELU = 0, 1, 2
+ACT_NONE, ACT_RELU, ACT_PRELU, ACT_PRELU_SUM = 0, 1, 2, 3
 
 _DTYPE = {torch.float32: VSRK_F32, torch.bfloat16: VSRK_BF16, torch.float16: VSRK_F16}
 
@@ -92,6 +92,7 @@ _SIGS = {
     "vsrk_view_to_ncdhw": (C.c_int, [_T5, _P, C.c_int32, _P]),
     "vsrk_relu_bwd": (C.c_int, [_T5, _T5, _T5, _P]),
     "vsrk_add": (C.c_int, [_T5, _T5, _T5, _P]),
+    "vsrk_sub": (C.c_int, [_T5, _T5, _T5, _P]),
     "vsrk_loss_workspace_size": (C.c_size_t, [C.c_int64]),
     "vsrk_loss_fwd": (C.c_int, [C.c_int32, C.c_float, _P, _P, C.c_int64, _P, _P, C.c_size_t, _P]),
     "vsrk_loss_bwd": (C.c_int, [C.c_int32, C.c_float, _P, _P, C.c_int64, _P, _P, C.c_int32, _P]),

@@ -63,7 +63,8 @@ __global__ __launch_bounds__(NTHR) void conv_fwd_kernel(ConvArgs a) {
   float* lsc = lbias_all + a.cout_pad;
   float* lsh = lsc + a.cin_pad;
   const bool relu_in = (a.prologue & VSRK_PRO_RELU) != 0;
-  const float aslope = a.act == VSRK_ACT_PRELU ? *a.act_param : 0.f;
+  const bool sumact = a.act == VSRK_ACT_PRELU_SUM;  // PReLU of the sum: applied after the residual add
+  const float aslope = (a.act == VSRK_ACT_PRELU || sumact) ? *a.act_param : 0.f;
   const float mslope = a.mask_slope ? *a.mask_slope : 0.f;
   if (a.prologue) stage_prologue(lsc, lsh, a.prologue, a.pro_scale, a.pro_shift, a.cin, a.cin_pad, tid, NTHR);
   for (int i = tid; i < a.cout_pad; i += NTHR) {
@@ -255,6 +256,7 @@ __global__ __launch_bounds__(NTHR) void conv_fwd_kernel(ConvArgs a) {
               t = act_apply(a.act, t, aslope);
               if (a.has_mask) t = mask_apply(m[e], t, mslope);
               if (a.has_res) t += rr[e];
+              if (sumact) t = t > 0.f ? t : aslope * t;
               if (a.accumulate) t += o[e];
               v[e] = t;
             }
@@ -486,8 +488,11 @@ extern "C" int vsrk_conv_fwd(const vsrk_conv_desc* d, const vsrk_tensor5* x, con
   VSRK_CHECK(x->n == y->n, "conv_fwd: batch mismatch");
   VSRK_CHECK(x->h < 32768 && x->w < 32768, "conv_fwd: spatial size too large");
   VSRK_CHECK(!(d->prologue & VSRK_PRO_AFFINE) || (pro_scale && pro_shift), "conv_fwd: affine prologue needs scale/shift");
-  VSRK_CHECK(d->act != VSRK_ACT_PRELU || d->act_param, "conv_fwd: PReLU activation needs act_param");
-  VSRK_CHECK(d->act >= VSRK_ACT_NONE && d->act <= VSRK_ACT_PRELU, "conv_fwd: bad act %d", d->act);
+  VSRK_CHECK(d->act >= VSRK_ACT_NONE && d->act <= VSRK_ACT_PRELU_SUM, "conv_fwd: bad act %d", d->act);
+  VSRK_CHECK((d->act != VSRK_ACT_PRELU && d->act != VSRK_ACT_PRELU_SUM) || d->act_param,
+             "conv_fwd: PReLU activation needs act_param");
+  VSRK_CHECK(d->act != VSRK_ACT_PRELU_SUM || (residual && !mask && !d->accumulate),
+             "conv_fwd: PReLU of the sum needs a residual and takes no mask / accumulate");
   const int yr = y->shuffle > 1 ? y->shuffle : 1;
   VSRK_CHECK(yr == 1 || (y->c / (yr * yr)) % 4 == 0, "conv_fwd: shuffled output needs c/r^2 %% 4 == 0");
   if (residual) {
@@ -552,7 +557,7 @@ extern "C" int vsrk_conv_fwd(const vsrk_conv_desc* d, const vsrk_tensor5* x, con
   }
   const int fast = vsrk_conv_fwd_fast(d, x, w_packed, bias, pro_scale, pro_shift, residual, mask, y, s);
   if (fast != 0) {
-    logd("fast");
+    logd(fast == 2 ? "roll" : "fast");
     return fast > 0 ? VSRK_OK : -fast;
   }
   logd("tile");

@@ -225,6 +225,7 @@ static int fwd_pw_impl(const vsrk_conv_desc* d, const vsrk_tensor5* x, const voi
   if (d->kd != 1 || d->kh != 1 || d->kw != 1 || d->pd || d->ph || d->pw) return 0;
   if (residual || d->bias_perm_r > 1) return 0;
   if (d->act == VSRK_ACT_PRELU && !d->act_param) return 0;
+  if (d->act < VSRK_ACT_NONE || d->act > VSRK_ACT_PRELU) return 0;  // (PReLU of the sum: the tile kernel)
   if (x->n != y->n || x->d != y->d || x->h != y->h || x->w != y->w) return 0;
   if (!dhw_dense(x) || !dhw_dense(y) || (mask && !same_geo(mask, y))) return 0;
   if (x->c % 8 || y->c % 4 || !chunk_ok(x, 2)) return 0;

@@ -140,6 +140,13 @@ static int roll_fwd_one(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vo
       return 0;
   }
   if (d->act == VSRK_ACT_PRELU && (k3 || !d->act_param)) return 0;
+  // PReLU of the sum (RBPN's block tail): the plain 2-D form with a residual
+  // operand only; an unknown activation code is nobody's
+  const bool sumact = d->act == VSRK_ACT_PRELU_SUM;
+  if (d->act < VSRK_ACT_NONE || d->act > VSRK_ACT_PRELU_SUM) return 0;
+  if (sumact && (k3 || !d->act_param || !residual || mask || d->accumulate || d->prologue || x->shuffle > 1 ||
+                 y->shuffle > 1 || bnred))
+    return 0;
   if (k3 && (residual || mask || d->accumulate)) return 0;
   // a single output depth from three slices (DUF's last unit): the depth-
   // folded 2-D form (conv_roll_fold.hip)
@@ -301,7 +308,7 @@ static int roll_fwd_one(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vo
   const int grid = (int)vsrk_capped_grid(std::min<int64_t>(ntiles, vsrk_num_cus()));
   const bool relu = d->act == VSRK_ACT_RELU;
   const int em = (residual ? RE_RES : 0) | (mask ? (pmask ? RE_PMASK : RE_MASK) : 0) | (d->accumulate ? RE_ACC : 0) |
-                 (relu ? RE_RELU : 0) | (d->act == VSRK_ACT_PRELU ? RE_PRELU : 0);
+                 (relu ? RE_RELU : 0) | (d->act == VSRK_ACT_PRELU ? RE_PRELU : 0) | (sumact ? RE_SUMACT : 0);
   a.mask_slope = d->mask_slope;
   if (pmask) {
     if ((size_t)grid * RNW > slope->cap) return 0;
@@ -361,6 +368,7 @@ static int roll_fwd_one(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vo
       case 0: return launch_roll<1, 2, 0, 0, SP_NONE, H>(a, lds, grid, s);
       case RE_RELU: return launch_roll<1, 2, 0, RE_RELU, SP_NONE, H>(a, lds, grid, s);
       case RE_RES: return launch_roll<1, 2, 0, RE_RES, SP_NONE, H>(a, lds, grid, s);
+      case RE_RES | RE_SUMACT: return launch_roll<1, 2, 0, RE_RES | RE_SUMACT, SP_NONE, H>(a, lds, grid, s);
       case RE_MASK: return launch_roll<1, 2, 0, RE_MASK, SP_NONE, H>(a, lds, grid, s);
       case RE_RES | RE_ACC: return launch_roll<1, 2, 0, RE_RES | RE_ACC, SP_NONE, H>(a, lds, grid, s);
       case RE_PMASK: return launch_roll<1, 2, 0, RE_PMASK, SP_NONE, H>(a, lds, grid, s);

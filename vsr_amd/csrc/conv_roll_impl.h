@@ -182,7 +182,10 @@ struct RollGeo {
 // with dy' = out * (bnx * scale + shift > 0), xhat = (bnx - mean) * invstd
 // (the per-tile partials hold sum dy' (bnx - mean); the final kernel scales
 // by invstd)
-enum { RE_RES = 1, RE_MASK = 2, RE_ACC = 4, RE_RELU = 8, RE_PRELU = 16, RE_PMASK = 32, RE_BNRED = 64 };
+// RE_SUMACT (2-D, with RE_RES): the PReLU applied to the sum, out =
+// prelu(fma(acc, out_scale, bias*out_scale) + residual) -- the tail of RBPN's
+// ResnetBlock (rbp_net.py:252-255); the residual arrives by RE_RES's route
+enum { RE_RES = 1, RE_MASK = 2, RE_ACC = 4, RE_RELU = 8, RE_PRELU = 16, RE_PMASK = 32, RE_BNRED = 64, RE_SUMACT = 128 };
 // sub-pixel operand (2-D forms): none, input view, output view.  SP_FOLD:
 // the depth-folded form of a Conv3d 3x3x3 with one output depth from three
 // input slices (DUF's last unit, padding (0, 1, 1), duf_net.py:214): a 3x3
@@ -267,6 +270,8 @@ template <int KD, int NT, int PRO, int EM, int SP, typename H, int WR>
 __global__ __launch_bounds__(RNW * 64, RNW / 4) void conv_roll_kernel(RollArgs a) {
   static_assert(SP == SP_NONE || KD == 1, "sub-pixel views: 2-D form only");
   static_assert(!WR || SP == SP_NONE, "resident weights: plain views only");
+  static_assert(!(EM & RE_SUMACT) || (KD == 1 && (EM & RE_RES) && !(EM & (RE_MASK | RE_ACC | RE_PMASK | RE_PRELU | RE_RELU))),
+                "PReLU of the sum: 2-D, residual only");
   using G = RollGeo<KD, NT, WR>;
   constexpr int RNQ = G::NQ, RSLOT = G::SLOT, NACC = G::NACC;
   // the transposed epilogue parks a row in two halves (2 KB of scratch per
@@ -661,7 +666,7 @@ __global__ __launch_bounds__(RNW * 64, RNW / 4) void conv_roll_kernel(RollArgs a
   };
 
   const float osc = a.out_scale;
-  const float pslope = (EM & RE_PRELU) ? *a.act_param : 0.f;
+  const float pslope = (EM & (RE_PRELU | RE_SUMACT)) ? *a.act_param : 0.f;
   const float mslope = (EM & RE_PMASK) ? *a.mask_slope : 0.f;
   float sacc = 0.f;  // RE_PMASK: this lane's sum_{mask < 0} out * mask
   auto slope_out = [&](float v) __attribute__((always_inline)) {  // the wave's partial, at its end
@@ -826,6 +831,10 @@ __global__ __launch_bounds__(RNW * 64, RNW / 4) void conv_roll_kernel(RollArgs a
             Chunk<H>::unpack(rv, rr);
 #pragma unroll
             for (int e = 0; e < 8; ++e) t[e] += rr[e];
+            if constexpr (EM & RE_SUMACT) {
+#pragma unroll
+              for (int e = 0; e < 8; ++e) t[e] = t[e] > 0.f ? t[e] : pslope * t[e];
+            }
           }
           if constexpr ((EM & RE_ACC) && !(EM & RE_PMASK)) {
             float o[8];
@@ -941,6 +950,10 @@ __global__ __launch_bounds__(RNW * 64, RNW / 4) void conv_roll_kernel(RollArgs a
           Chunk<H>::unpack(rv, rr);
 #pragma unroll
           for (int e = 0; e < 8; ++e) t[e] += rr[e];
+          if constexpr (EM & RE_SUMACT) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) t[e] = t[e] > 0.f ? t[e] : pslope * t[e];
+          }
         }
         if constexpr ((EM & RE_ACC) && !(EM & RE_PMASK)) {
           float o[8];

@@ -637,6 +637,7 @@ int vsrk_conv_fwd_thin(const vsrk_conv_desc* d, const vsrk_tensor5* x, const voi
                        const vsrk_tensor5* mask, const vsrk_tensor5* y, hipStream_t s) {
   if (vsrk_path_mode(VSRK_PATH_THIN) == 0) return 0;
   if (!vsrk_is16(x->dtype)) return 0;
+  if (d->act < VSRK_ACT_NONE || d->act > VSRK_ACT_PRELU) return 0;  // (PReLU of the sum: the tile kernel)
   if (const int st = vsrk_conv_fwd_stencil(d, x, w_packed, bias, residual, mask, y, s)) return st;
   if (const int st = vsrk_conv_fwd_stencil_out(d, x, w_packed, bias, residual, mask, y, s)) return st;
   if (x->shuffle > 1 || y->shuffle > 1 || d->bias_perm_r > 1) return 0;

@@ -147,6 +147,18 @@ __global__ void add_kernel(View a, View b, View o, int64_t total) {
   reinterpret_cast<T*>(o.ptr)[view_off(o, n, d, h, w, c)] = from_f32<T>(av + bv);
 }
 
+template <typename T>
+__global__ void sub_kernel(View a, View b, View o, int64_t total) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int c = idx % a.c;
+  int n, d, h, w;
+  decode_voxel(idx / a.c, a, n, d, h, w);
+  const float av = to_f32<T>(reinterpret_cast<const T*>(a.ptr)[view_off(a, n, d, h, w, c)]);
+  const float bv = to_f32<T>(reinterpret_cast<const T*>(b.ptr)[view_off(b, n, d, h, w, c)]);
+  reinterpret_cast<T*>(o.ptr)[view_off(o, n, d, h, w, c)] = from_f32<T>(av - bv);
+}
+
 // nn.Tanh on a view (FNet's flow head, frvsr_net.py:143): BWD = 0 y = tanh(a),
 // BWD = 1 out = b * (1 - a^2) with a the forward output and b its gradient
 template <typename T, int BWD>
@@ -376,6 +388,21 @@ extern "C" int vsrk_add(const vsrk_tensor5* a, const vsrk_tensor5* b, const vsrk
 static bool same_geometry(const vsrk_tensor5* a, const vsrk_tensor5* b) {
   return a->dtype == b->dtype && a->n == b->n && a->d == b->d && a->h == b->h && a->w == b->w && a->c == b->c &&
          a->shuffle == b->shuffle;
+}
+
+extern "C" int vsrk_sub(const vsrk_tensor5* a, const vsrk_tensor5* b, const vsrk_tensor5* out, void* stream) {
+  VSRK_CHECK(a && b && out && a->ptr && b->ptr && out->ptr, "sub: null argument");
+  VSRK_CHECK(same_geometry(a, b) && same_geometry(a, out), "sub: views differ in shape or dtype");
+  const int64_t total = nvox(a) * a->c;
+  if (total == 0) return VSRK_OK;
+  VSRK_CHECK(total <= ((int64_t)1 << 39), "sub: too large (%lld elements)", (long long)total);
+  hipStream_t s = (hipStream_t)stream;
+  vsrk_dispatch_dtype(a->dtype, [&](auto tag) {
+    sub_kernel<decltype(tag)><<<(unsigned)ceil_div64(total, 256), 256, 0, s>>>(make_view(a), make_view(b),
+                                                                               make_view(out), total);
+  });
+  VSRK_LAUNCH_CHECK("sub");
+  return VSRK_OK;
 }
 
 template <int BWD>

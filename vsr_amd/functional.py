@@ -14,10 +14,11 @@ import ctypes as C
 import torch
 
 from . import _native as N
-from ._native import ACT_NONE, ACT_PRELU, ACT_RELU, PRO_AFFINE, PRO_AFFINE_RELU, PRO_NONE, PRO_RELU  # noqa: F401
+from ._native import (ACT_NONE, ACT_PRELU, ACT_PRELU_SUM, ACT_RELU, PRO_AFFINE, PRO_AFFINE_RELU,  # noqa: F401
+                      PRO_NONE, PRO_RELU)
 
 __all__ = [
-    "pack_weight", "conv", "conv_wgrad", "to_view", "from_view", "relu_bwd", "add",
+    "pack_weight", "conv", "conv_wgrad", "to_view", "from_view", "relu_bwd", "add", "sub",
     "loss_fwd", "loss_bwd", "psnr", "ssim", "workspace", "LOSS_KINDS",
     "bn_stats", "bn_finalize", "bn_fold_running", "bn_apply", "bn_relu_bwd_reduce", "bn_relu_bwd_apply",
     "duf_dynfilter_fwd", "duf_dynfilter_bwd",
@@ -243,7 +244,9 @@ def conv(x: torch.Tensor, wp: torch.Tensor, y: torch.Tensor, k, pad, *, bias: to
     """y[...] = epilogue(conv(prologue(x), W) + bias); writes into the given y view.
 
     residual/mask are views with y's logical shape (and y_shuffle addressing).
-    act=ACT_PRELU reads its slope from the device scalar act_param; with
+    act=ACT_PRELU reads its slope from the device scalar act_param;
+    act=ACT_PRELU_SUM applies that PReLU after the residual is added (a
+    residual is required, no mask / accumulate); with
     mask_slope the mask keeps mask_slope * value where mask <= 0 (PReLU
     backward) instead of zero (ReLU backward).  bias_r overrides the bias
     order (default: torch pixel-shuffle order of a y_shuffle output).
@@ -485,6 +488,14 @@ def add(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     lib = _lib()
     x, y, z = N.t5(a), N.t5(b), N.t5(out)
     N.check(lib.vsrk_add(C.byref(x), C.byref(y), C.byref(z), N.stream_ptr(a.device)), "add")
+    return out
+
+
+def sub(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out = a - b on views of one shape and dtype (out may be a or b)."""
+    lib = _lib()
+    x, y, z = N.t5(a), N.t5(b), N.t5(out)
+    N.check(lib.vsrk_sub(C.byref(x), C.byref(y), C.byref(z), N.stream_ptr(a.device)), "sub")
     return out
 
 

@@ -7,6 +7,8 @@ from .duf_net import DUFNet
 from .edsr_net import EDSRNet
 from .edvr_net import EDVRNet
 from .frvsr_net import FRVSRNet
+from .rbp_net import RBPNet
 from .srfb_net import SRFBNet
 
-__all__ = ["BaseNet", "EDSRNet", "DUFNet", "DRFNet", "DRFSISRNet", "SRFBNet", "Bicubic", "FRVSRNet", "EDVRNet"]
+__all__ = ["BaseNet", "EDSRNet", "DUFNet", "DRFNet", "DRFSISRNet", "SRFBNet", "Bicubic", "FRVSRNet", "EDVRNet",
+           "RBPNet"]
