@@ -48,6 +48,15 @@ class BaseNet(nn.Module):
         self._side_used = False
         self._side_keep: list = []  # operands of side-stream launches captured into a graph (see _on_wgrad_stream)
         self._packers: dict = {}
+        self._consts: dict = {}
+
+    def _const(self, dev, value: float) -> torch.Tensor:
+        """A constant fp32 device scalar (a fixed LeakyReLU slope as a conv's
+        act_param), created once per device."""
+        key = (dev.type, dev.index, value)
+        if key not in self._consts:
+            self._consts[key] = torch.full((1,), value, dtype=torch.float32, device=dev)
+        return self._consts[key]
 
     # -- gradient plumbing used by the subclasses' backward passes ----------
     def _grad_buffer(self, p: torch.Tensor) -> torch.Tensor:

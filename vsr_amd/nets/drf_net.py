@@ -55,10 +55,7 @@ import torch.nn as nn
 
 from .. import functional as F
 from .base_net import BaseNet
-
-K1, P0 = (1, 1, 1), (0, 0, 0)
-K3, P1 = (1, 3, 3), (0, 1, 1)
-_PROJ = {2: (6, 2, 2), 3: (7, 3, 2), 4: (8, 4, 2), 8: (12, 8, 2)}  # drf_net.py:70-77
+from .tape import K1, K3, P0, P1, PROJ, subpixel_cache
 
 
 def _prelu():
@@ -83,7 +80,7 @@ class _FBlock(nn.Module):
         self.in_block.add_module("prelu", _prelu())
         self.up_blocks = nn.ModuleList()
         self.down_blocks = nn.ModuleList()
-        k, s, p = _PROJ[upscale_factor]
+        k, s, p = PROJ[upscale_factor]
         for i in range(num_groups):
             up, down = nn.Sequential(), nn.Sequential()
             if i == 0:
@@ -201,23 +198,16 @@ class _DRFBase(BaseNet):
     def _packer(self):
         cd = self.compute_dtype
         cache: dict = {}
+        sp_ = subpixel_cache(cd)
 
         def pw(conv, mode=0, perm_r=1):
-            key = ("w", id(conv.weight), mode, perm_r)
+            key = (id(conv.weight), mode, perm_r)
             if key not in cache:
                 cache[key] = F.pack_weight(conv.weight, mode, cd, perm_r=perm_r)
             return cache[key]
 
         def sp(conv, transposed, mode=0):
-            k, s, p = _PROJ[self.upscale_factor]
-            key = ("eq", id(conv.weight))
-            if key not in cache:
-                cache[key] = F.subpixel_conv_weight(conv.weight, conv.bias, k, s, p, transposed)
-            weq, beq = cache[key]
-            pkey = ("sp", id(conv.weight), mode)
-            if pkey not in cache:
-                cache[pkey] = F.pack_weight(weq, mode, cd)
-            return cache[pkey], beq
+            return sp_(conv, PROJ[self.upscale_factor], transposed, mode)
 
         return pw, sp
 
@@ -312,7 +302,7 @@ class _DRFBase(BaseNet):
         frames = self._frames(inputs)
         cd = self.compute_dtype
         f, G = self.num_features, self.num_groups
-        k, s, p = _PROJ[self.upscale_factor]
+        k, s, p = PROJ[self.upscale_factor]
         b, cin, h, w = frames[0].shape
         dev = frames[0].device
         H, W = h * s, w * s
@@ -405,7 +395,7 @@ class _DRFBase(BaseNet):
     def _backward(self, tape: dict, gys) -> dict:
         cd = self.compute_dtype
         f, G = self.num_features, self.num_groups
-        k, s, p = _PROJ[self.upscale_factor]
+        k, s, p = PROJ[self.upscale_factor]
         b, h, w = tape["shape"]
         H, W = h * s, w * s
         pw, sp = tape["packer"]

@@ -25,9 +25,7 @@ import torch.nn as nn
 
 from .. import functional as F
 from .base_net import BaseNet
-
-K3 = (1, 3, 3)
-P1 = (0, 1, 1)
+from .tape import K3, P1
 
 
 def _up_steps(r: int) -> list[int]:

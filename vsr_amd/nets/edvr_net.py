@@ -44,9 +44,9 @@ How the step runs (the structure the reference allows):
     input (computed on the device, no host read) and the output is cropped,
     in torch plumbing, as the reference does (:73-80, 141-144).
 
-The backward pass is an op-level tape: every forward op appends its reverse,
-and the reverses run last to first, summing the gradients of a tensor with
-several consumers as they arrive.
+The backward pass is an op-level tape (tape.py); the gradients of a tensor
+with several consumers are summed as they arrive (_Bwd.acc), so that only one
+is held at a time.
 
 Deliberately not reproduced: the pack's `offset_mean > 100` warning
 (deform_conv.py:285-287) costs a host read per DCN per step.
@@ -64,16 +64,10 @@ import torch.nn as nn
 
 from .. import functional as F
 from .base_net import BaseNet
+from .tape import K1, K3, P0, P1, Bwd, cp, empty_view, recorder, subpixel_cache
 
-K3, P1 = (1, 3, 3), (0, 1, 1)
-K1, P0 = (1, 1, 1), (0, 0, 0)
 _S2 = (3, 2, 1)  # kernel, stride, padding of the stride-2 feature convs
 LEAKY, RELU = "leaky", "relu"
-
-
-def _cp(c: int) -> int:
-    """Channels of the storage a c-channel view lives in (whole 16-byte chunks)."""
-    return -(-c // 8) * 8
 
 
 class _ResBlock(nn.Module):
@@ -145,33 +139,21 @@ class TSAFusion(nn.Module):
         self.sAtt_add_2 = nn.Conv2d(nf, nf, 1, 1)
 
 
-class _Bwd:
-    """State of one reverse pass: the gradients that have arrived per tensor,
-    the parameter gradient buffers and the packed data-gradient weights."""
+class _Bwd(Bwd):
+    """The reverse pass with the packed data-gradient weights pk; a tensor's
+    gradient contributions are summed on arrival, left to right, which frees
+    both operands there (the peak at 5 x 128 x 128 x 64 depends on it)."""
 
-    def __init__(self, net, dev, pk):
-        self.net, self.dev, self.pk = net, dev, pk
+    def __init__(self, net, dev, pk, sp):
+        super().__init__(net)
+        self.pk, self.sp = pk, sp
         self.cd = net.compute_dtype
-        self.G: dict = {}
-        self.bufs: dict = {}
-        self.slope = net._slope(dev)
+        self.slope = net._const(dev, 0.1)
         self.dummy = torch.empty(1, dtype=torch.float32, device=dev)
-
-    def new_like(self, t, dtype=None, zero=False):
-        mk = torch.zeros if zero else torch.empty
-        return mk((*t.shape[:4], _cp(t.shape[4])), dtype=dtype or t.dtype, device=self.dev)[..., :t.shape[4]]
 
     def acc(self, t, g):
         old = self.G.get(id(t))
-        self.G[id(t)] = g if old is None else F.add(old, g, self.new_like(g))
-
-    def take(self, t):
-        return self.G.pop(id(t))
-
-    def gbuf(self, p):
-        if id(p) not in self.bufs:
-            self.bufs[id(p)] = (p, self.net._grad_buffer(p))
-        return self.bufs[id(p)][1]
+        self.G[id(t)] = [g] if old is None else [F.add(old[0], g, self.new_like(g))]
 
     def act_bwd(self, act, y, g):
         if g.dtype != self.cd:  # the fp32 gradient of an fp32 view (offsets and masks), rounded for the conv's backward
@@ -183,13 +165,6 @@ class _Bwd:
         if act == RELU:
             return F.relu_bwd(y, g, self.new_like(g))
         return g
-
-    def route(self, x, parts, gx):
-        if parts is None:
-            self.acc(x, gx)
-        else:
-            for t, lo, hi in parts:
-                self.acc(t, gx[..., lo:hi])
 
 
 class EDVRNet(BaseNet):
@@ -230,16 +205,9 @@ class EDVRNet(BaseNet):
         self.HRconv = nn.Conv2d(64, 64, 3, 1, 1)
         self.conv_last = nn.Conv2d(64, out_channels, 3, 1, 1)
         self.lrelu = nn.LeakyReLU(negative_slope=0.1, inplace=True)
-        self._slopes: dict = {}
         self._w1: dict = {}
 
     # ------------------------------------------------------------------
-    def _slope(self, dev) -> torch.Tensor:
-        key = (dev.type, dev.index)
-        if key not in self._slopes:
-            self._slopes[key] = torch.full((1,), 0.1, dtype=torch.float32, device=dev)
-        return self._slopes[key]
-
     def _packs(self):
         p = self.pcd_align
         return [p.L3_dcnpack, p.L2_dcnpack, p.L1_dcnpack, p.cas_dcnpack]
@@ -283,18 +251,14 @@ class EDVRNet(BaseNet):
             padded[..., top:top + H0, left:left + W0] = X
             X = padded
         BN = B * N
-        slope = self._slope(dev)
+        slope = self._const(dev, 0.1)
         pk = self._pack_weights(self._specs(0))
-        ops: list | None = [] if tape is not None else None
+        sp = subpixel_cache(cd)
+        ops, push = recorder(tape is not None)
         pa, ts = self.pcd_align, self.tsa_fusion
 
         def new(b, hh, ww, ch, dtype=cd, zero=False):
-            mk = torch.zeros if zero else torch.empty
-            return mk((b, 1, hh, ww, _cp(ch)), dtype=dtype, device=dev)[..., :ch]
-
-        def push(fn):
-            if ops is not None:
-                ops.append(fn)
+            return empty_view((b, 1, hh, ww), ch, dtype, dev, zero)
 
         def conv(x, m, y, act=None, residual=None, parts=None, need_dx=True, shuffle=1):
             """y = act(conv(x) + bias [+ residual]); parts: the channel slices of x that are tensors of their own."""
@@ -310,8 +274,7 @@ class EDVRNet(BaseNet):
                     # gradient missed its bound (edvr_x4_pad), so this conv's backward runs in fp32
                     x32 = bk.new_like(x, torch.float32, zero=True)
                     x32.copy_(x)
-                    dw = bk.gbuf(m.weight)
-                    F.conv_wgrad(x32, g, k, p, dw.view(*dw.shape[:2], 1, *dw.shape[2:]), bk.gbuf(m.bias))
+                    bk.conv_wgrad(m, x32, g, k, p)
                     gx = F.conv(g, F.pack_weight(m.weight, 1, torch.float32), bk.new_like(x, torch.float32), k, p)
                     g16 = bk.new_like(x)
                     g16.copy_(gx)
@@ -320,9 +283,7 @@ class EDVRNet(BaseNet):
                 g = bk.act_bwd(act, y, g)
                 if residual is not None:
                     bk.acc(residual, g)
-                dw = bk.gbuf(m.weight)
-                F.conv_wgrad(x, g, k, p, dw.view(*dw.shape[:2], 1, *dw.shape[2:]), bk.gbuf(m.bias), perm_r=shuffle,
-                             dy_shuffle=shuffle)
+                bk.conv_wgrad(m, x, g, k, p, perm_r=shuffle, dy_shuffle=shuffle)
                 if need_dx:
                     gx = F.conv(g, bk.pk[(id(m.weight), 1, shuffle)], bk.new_like(x), k, p, x_shuffle=shuffle)
                     bk.route(x, parts, gx)
@@ -332,17 +293,14 @@ class EDVRNet(BaseNet):
 
         def sconv(x, m, y):
             """LeakyReLU(Conv2d(3, stride 2, pad 1)): a sub-pixel 3x3 conv over the shuffle-2 view of x."""
-            k_, s_, p_ = _S2
-            weq, beq = F.subpixel_conv_weight(m.weight, m.bias, k_, s_, p_, False)
-            F.conv(x, F.pack_weight(weq, 0, cd), y, K3, P1, bias=beq, x_shuffle=s_, act=F.ACT_PRELU, act_param=slope)
+            s_ = _S2[1]
+            wq, beq = sp(m, _S2, False)
+            F.conv(x, wq, y, K3, P1, bias=beq, x_shuffle=s_, act=F.ACT_PRELU, act_param=slope)
 
             def bwd(bk):
                 g = bk.act_bwd(LEAKY, y, bk.take(y))
-                dweq = torch.empty((weq.shape[0], weq.shape[1], 1, 3, 3), dtype=torch.float32, device=dev)
-                dbeq = torch.empty(weq.shape[0], dtype=torch.float32, device=dev)
-                F.conv_wgrad(x, g, K3, P1, dweq, dbeq, x_shuffle=s_)
-                F.subpixel_wgrad_fold(dweq, dbeq, bk.gbuf(m.weight), bk.gbuf(m.bias), k_, s_, p_, False)
-                bk.acc(x, F.conv(g, F.pack_weight(weq, 1, cd), bk.new_like(x), K3, P1, y_shuffle=s_))
+                bk.subpixel_wgrad(m, x, g, _S2, False, tap_skip=False)
+                bk.acc(x, F.conv(g, bk.sp(m, _S2, False, 1)[0], bk.new_like(x), K3, P1, y_shuffle=s_))
 
             push(bwd)
             return y
@@ -403,8 +361,8 @@ class EDVRNet(BaseNet):
                 g = bk.act_bwd(act, y, bk.take(y))
                 gcols = F.conv(g, bk.pk[(id(w1), 1, 1)], bk.new_like(cols), K1, P0)
                 dw1 = torch.empty((nf, 9 * nf, 1, 1, 1), dtype=torch.float32, device=dev)
-                F.conv_wgrad(cols, g, K1, P0, dw1, bk.gbuf(pack.bias))
-                bk.gbuf(pack.weight).copy_(dw1.view(nf, 3, 3, nf).permute(0, 3, 1, 2))
+                F.conv_wgrad(cols, g, K1, P0, dw1, bk.buf(pack.bias)[0])
+                bk.buf(pack.weight)[0].copy_(dw1.view(nf, 3, 3, nf).permute(0, 3, 1, 2))
                 bk.acc(om, F.dcn_view_coord_grad(geo, x, gcols, om, bk.new_like(om, zero=True)))
                 gx = torch.zeros(x.shape, dtype=torch.float32, device=dev)
                 F.dcn_view_col2im(geo, gcols, om, gx)
@@ -415,7 +373,7 @@ class EDVRNet(BaseNet):
 
         h2, w2, h3, w3 = H // 2, W // 2, H // 4, W // 4
         # ---- features of all B N frames; each level's result is the first half of its concat buffer
-        x0 = F.to_view(X.reshape(BN, C, H, W), cd, cpad=_cp(C))[..., :C]
+        x0 = F.to_view(X.reshape(BN, C, H, W), cd, cpad=cp(C))[..., :C]
         c1, l1, r1, p1 = cat2(BN, H, W)
         c2, l2, r2, p2 = cat2(BN, h2, w2)
         c3, l3, r3, p3 = cat2(BN, h3, w3)
@@ -538,7 +496,7 @@ class EDVRNet(BaseNet):
                              "out_channels")
         F.upsample2d(X[:, cen].contiguous(), y, "bilinear", False, 4, accumulate=True)
         if tape is not None:
-            tape.update(ops=ops, yv=yv, geom=(B, H, W, H0, W0, top, left))
+            tape.update(ops=ops, yv=yv, sp=sp, geom=(B, H, W, H0, W0, top, left))
         if hd or wd:
             y = y[..., top * 4:(top + H0) * 4, left * 4:(left + W0) * 4].contiguous()
         return y
@@ -553,11 +511,5 @@ class EDVRNet(BaseNet):
             full[..., top * 4:(top + H0) * 4, left * 4:(left + W0) * 4] = g
             g = full
         co = self.out_channels
-        bk = _Bwd(self, dev, self._pack_weights(self._specs(1)))
-        bk.acc(tape["yv"], F.to_view(g, self.compute_dtype, cpad=_cp(co))[..., :co])
-        for op in reversed(tape["ops"]):
-            op(bk)
-        out: dict = {}
-        for p, gb in bk.bufs.values():
-            self._grad_done(out, p, gb)
-        return out
+        bk = _Bwd(self, dev, self._pack_weights(self._specs(1)), tape["sp"])
+        return bk.run(tape["ops"], tape["yv"], F.to_view(g, self.compute_dtype, cpad=cp(co))[..., :co])

@@ -25,8 +25,11 @@ through time):
     is warped from the LOW-resolution flow (flow_up = r interpolates it inside
     the kernel) and stored through SpaceToDepth(r) straight into the head's
     concat input (s2d = r); the deconvs are 3x3 sub-pixel convs written through
-    shuffle-2 views.  Its backward runs frame by frame in any order; weight
-    gradients accumulate over the frames in a fixed order.
+    shuffle-2 views.  Its backward runs frame by frame, in ascending t: the
+    shared weights' gradients accumulate over the frames in that order, which
+    is why the two backward loops are written out and are not a reverse tape
+    (tape.py supplies the gradient ledger, the sub-pixel weight cache and the
+    view allocation only).
   * The warp's space-to-depth channel order is (i r + j) C + c', the
     reference's c' r^2 + i r + j: equal for C = 1; for C > 1 the head weight's
     input channels are permuted when packed and its gradient permuted back.
@@ -41,15 +44,9 @@ import torch.nn as nn
 
 from .. import functional as F
 from .base_net import BaseNet
+from .tape import K3, P1, ParamGrads, cp, empty_view, subpixel_cache
 
-K3 = (1, 3, 3)
-P1 = (0, 1, 1)
 _DECONV = (3, 2, 1)  # kernel, stride, padding of the tail's deconvs (output_padding 1 = s - k + 2p)
-
-
-def _cp(c: int) -> int:
-    """Channels of the storage a c-channel view lives in (whole 16-byte chunks)."""
-    return -(-c // 8) * 8
 
 
 class _ResBlock(nn.Module):
@@ -127,7 +124,6 @@ class FRVSRNet(BaseNet):
         for m in self.modules():
             if m.__class__.__name__.find("Conv") != -1:
                 nn.init.xavier_uniform_(m.weight)
-        self._slopes: dict = {}
 
     # ------------------------------------------------------------------
     def forward(self, inputs):
@@ -143,12 +139,6 @@ class FRVSRNet(BaseNet):
 
     def _returns_list(self) -> bool:
         return True
-
-    def _slope(self, dev) -> torch.Tensor:
-        key = (dev.type, dev.index)
-        if key not in self._slopes:
-            self._slopes[key] = torch.full((1,), 0.2, dtype=torch.float32, device=dev)
-        return self._slopes[key]
 
     def _head_perm(self, dev):
         """Input-channel index of the reference's head weight for each channel of
@@ -170,12 +160,11 @@ class FRVSRNet(BaseNet):
         n, _, h, w = inputs[0].shape
         dev = inputs[0].device
         H, W, NT, rr = h * r, w * r, n * T, r * r
-        slope = self._slope(dev)
+        slope = self._const(dev, 0.2)
         sr, fn = self.srnet, self.fnet
 
         def new(b, hh, ww, ch, dtype=cd, zero=False):
-            mk = torch.zeros if zero else torch.empty
-            return mk((b, 1, hh, ww, _cp(ch)), dtype=dtype, device=dev)[..., :ch]
+            return empty_view((b, 1, hh, ww), ch, dtype, dev, zero)
 
         X = torch.stack([x.float() for x in inputs])                       # (T, n, c, h, w)
         prev = torch.cat([X[:1], X[:-1]])
@@ -194,7 +183,7 @@ class FRVSRNet(BaseNet):
         def P(conv):
             return pk[(id(conv.weight), 0, 1)]
 
-        cur = F.to_view(pair.reshape(NT, 2 * c, hp, wp), cd, cpad=_cp(2 * c))[..., :2 * c]
+        cur = F.to_view(pair.reshape(NT, 2 * c, hp, wp), cd, cpad=cp(2 * c))[..., :2 * c]
         ftape = []
         for kind, m in fops:
             b_, _, hh, ww, ch = cur.shape
@@ -212,19 +201,16 @@ class FRVSRNet(BaseNet):
         flow_cl = F.tanh(cur, cur)                                          # (NT, 1, hp, wp, 2) fp32, in place
         flow = flow_cl[:, 0, top:top + h, left:left + w].permute(0, 3, 1, 2).contiguous()   # (NT, 2, h, w)
         # ---- the T low-resolution warps, one launch (fp32 images)
-        prev_v = F.to_view(prev.reshape(NT, c, h, w), torch.float32, cpad=_cp(c))[..., :c]
+        prev_v = F.to_view(prev.reshape(NT, c, h, w), torch.float32, cpad=cp(c))[..., :c]
         lrw = F.flow_warp(prev_v, flow, new(NT, h, w, c, torch.float32), "border", False)
         lr_out = list(F.from_view(lrw).view(T, n, c, h, w).unbind(0))
         # ---- SR net, frame by frame
-        Xv = F.to_view(X.reshape(NT, c, h, w), cd, cpad=_cp(c))[..., :c]
+        Xv = F.to_view(X.reshape(NT, c, h, w), cd, cpad=cp(c))[..., :c]
         perm = self._head_perm(dev)
         hw_ = sr.head.conv.weight if perm is None else sr.head.conv.weight.detach()[:, perm].contiguous()
         head_p = F.pack_weight(hw_, 0, cd)
-        k_, s_, p_ = _DECONV
-        dec = []
-        for d in (sr.tail.deconv1, sr.tail.deconv2):
-            weq, beq = F.subpixel_conv_weight(d.weight, d.bias, k_, s_, p_, True)
-            dec.append((weq, beq, F.pack_weight(weq, 0, cd)))
+        sp = subpixel_cache(cd)
+        dec = [sp(d, _DECONV, True) for d in (sr.tail.deconv1, sr.tail.deconv2)]
         cin = c * (rr + 1)
         est = new(n, H, W, c, zero=True)                                    # the first estimate: zeros
         sr_out, stape = [], []
@@ -241,9 +227,9 @@ class FRVSRNet(BaseNet):
                 nxt = F.conv(a, P(c2), new(n, h, w, 64), K3, P1, bias=c2.bias, residual=x_)
                 saved.append((x_, a))
                 x_ = nxt
-            u1 = F.conv(x_, dec[0][2], new(n, 2 * h, 2 * w, 64), K3, P1, bias=dec[0][1], bias_r=1, y_shuffle=2,
+            u1 = F.conv(x_, dec[0][0], new(n, 2 * h, 2 * w, 64), K3, P1, bias=dec[0][1], bias_r=1, y_shuffle=2,
                         act=F.ACT_RELU)
-            u2 = F.conv(u1, dec[1][2], new(n, H, W, 64), K3, P1, bias=dec[1][1], bias_r=1, y_shuffle=2,
+            u2 = F.conv(u1, dec[1][0], new(n, H, W, 64), K3, P1, bias=dec[1][1], bias_r=1, y_shuffle=2,
                         act=F.ACT_RELU)
             tc = sr.tail.conv
             yv = F.conv(u2, P(tc), new(n, H, W, c, torch.float32), K3, P1, bias=tc.bias)
@@ -251,9 +237,9 @@ class FRVSRNet(BaseNet):
             sr_out.append(y)
             if tape is not None:
                 stape.append(dict(est=est, hin=hin, h0=h0, saved=saved, body=x_, u1=u1, u2=u2))
-            est = F.to_view(y, cd, cpad=_cp(c))[..., :c]
+            est = F.to_view(y, cd, cpad=cp(c))[..., :c]
         if tape is not None:
-            tape.update(ftape=ftape, flow_cl=flow_cl, flow=flow, prev_v=prev_v, stape=stape, dec=dec, perm=perm,
+            tape.update(ftape=ftape, flow_cl=flow_cl, flow=flow, prev_v=prev_v, stape=stape, sp=sp, perm=perm,
                         geom=(T, n, h, w, top, left, hp, wp))
         return sr_out + lr_out
 
@@ -266,21 +252,12 @@ class FRVSRNet(BaseNet):
         gsr, glr = grads[:T], grads[T:]
         flow = tape["flow"]
         dev = flow.device
-        slope = self._slope(dev)
+        slope = self._const(dev, 0.2)
         sr, fn = self.srnet, self.fnet
-        out: dict = {}
-        bufs: dict = {}
+        pg = ParamGrads(self)
 
         def new(b, hh, ww, ch, dtype=cd, zero=False):
-            mk = torch.zeros if zero else torch.empty
-            return mk((b, 1, hh, ww, _cp(ch)), dtype=dtype, device=dev)[..., :ch]
-
-        def gbuf(p):
-            """(gradient buffer of p, whether an earlier frame already wrote it)."""
-            seen = id(p) in bufs
-            if not seen:
-                bufs[id(p)] = (p, self._grad_buffer(p))
-            return bufs[id(p)][1], seen
+            return empty_view((b, 1, hh, ww), ch, dtype, dev, zero)
 
         pk = self._pack_weights([(m.weight, 1, 1) for k, m in fn.ops() if k in ("leaky", "plain")][1:]
                                 + [(m.weight, 1, 1) for m in self._sr_convs()])
@@ -292,50 +269,44 @@ class FRVSRNet(BaseNet):
             return F.relu_bwd(y, g, torch.empty_like(g))
 
         # ---- SR net, frame by frame (independent: the estimate and the frames carry no gradient)
-        k_, s_, p_ = _DECONV
-        dec = tape["dec"]
-        dec_d = [F.pack_weight(weq, 1, cd) for weq, _, _ in dec]
+        s_ = _DECONV[1]
+        dec_d = [tape["sp"](d, _DECONV, True, 1)[0] for d in (sr.tail.deconv1, sr.tail.deconv2)]
         perm = tape["perm"]
         hconv = sr.head.conv
         hw_ = hconv.weight if perm is None else hconv.weight.detach()[:, perm].contiguous()
         head_d = F.pack_weight(hw_, 1, cd)
         cin = c * (rr + 1)
         gflow = torch.zeros((NT, 2, h, w), dtype=torch.float32, device=dev)
-        dweq = torch.empty((s_ * s_ * 64, 64, 1, 3, 3), dtype=torch.float32, device=dev)
-        dbeq = torch.empty(s_ * s_ * 64, dtype=torch.float32, device=dev)
         ghr = torch.empty((n, 2, H, W), dtype=torch.float32, device=dev)
         for t in range(T):
             if gsr[t] is None:
                 continue
             rec = tape["stape"][t]
-            g = F.to_view(gsr[t].float(), cd, cpad=_cp(c))[..., :c]
+            g = F.to_view(gsr[t].float(), cd, cpad=cp(c))[..., :c]
             tc = sr.tail.conv
-            self._wgrad(gbuf, tc, rec["u2"], g)
+            pg.conv_wgrad(tc, rec["u2"], g, K3, P1)
             g = relu_bwd(rec["u2"], F.conv(g, D(tc), new(n, H, W, 64), K3, P1))
             for d, x_in, dd in ((sr.tail.deconv2, rec["u1"], dec_d[1]), (sr.tail.deconv1, rec["body"], dec_d[0])):
-                dw, acc = gbuf(d.weight)
-                db, _ = gbuf(d.bias)
-                F.conv_wgrad(x_in, g, K3, P1, dweq, dbeq, dy_shuffle=s_)
-                F.subpixel_wgrad_fold(dweq, dbeq, dw, db, k_, s_, p_, True, accumulate=acc)
+                pg.subpixel_wgrad(d, x_in, g, _DECONV, True, tap_skip=False)
                 hh, ww = x_in.shape[2], x_in.shape[3]
                 g = F.conv(g, dd, new(n, hh, ww, 64), K3, P1, x_shuffle=s_)
                 if d is sr.tail.deconv2:
                     g = relu_bwd(x_in, g)
             for blk, (x_in, a) in reversed(list(zip(sr.body, rec["saved"]))):
                 c1, c2 = blk.body.conv1, blk.body.conv2
-                self._wgrad(gbuf, c2, a, g)
+                pg.conv_wgrad(c2, a, g, K3, P1)
                 ga = relu_bwd(a, F.conv(g, D(c2), new(n, h, w, 64), K3, P1))
-                self._wgrad(gbuf, c1, x_in, ga)
+                pg.conv_wgrad(c1, x_in, ga, K3, P1)
                 g = F.conv(ga, D(c1), new(n, h, w, 64), K3, P1, residual=g)
             g = relu_bwd(rec["h0"], g)
             if perm is None:
-                self._wgrad(gbuf, hconv, rec["hin"], g)
+                pg.conv_wgrad(hconv, rec["hin"], g, K3, P1)
             else:  # in the warp's channel order, permuted back onto the reference's
                 # (one accumulate flag serves weight and bias: the scratch starts at zero)
                 tmp = torch.zeros_like(hconv.weight, dtype=torch.float32)
-                db, accb = gbuf(hconv.bias)
+                db, accb = pg.buf(hconv.bias)
                 F.conv_wgrad(rec["hin"], g, K3, P1, tmp.view(*tmp.shape[:2], 1, *tmp.shape[2:]), db, accumulate=accb)
-                dw, acc = gbuf(hconv.weight)
+                dw, acc = pg.buf(hconv.weight)
                 if acc:
                     dw.index_add_(1, perm, tmp)
                 else:
@@ -348,7 +319,7 @@ class FRVSRNet(BaseNet):
         # ---- the low-resolution warps, one launch, onto the same flow gradient
         if any(g_ is not None for g_ in glr):
             gl = torch.stack([g_.float() if g_ is not None else torch.zeros((n, c, h, w), device=dev) for g_ in glr])
-            glv = F.to_view(gl.reshape(NT, c, h, w), torch.float32, cpad=_cp(c))[..., :c]
+            glv = F.to_view(gl.reshape(NT, c, h, w), torch.float32, cpad=cp(c))[..., :c]
             F.flow_warp_bwd(tape["prev_v"], flow, glv, gflow, "border", False, accumulate=True)
         # ---- tanh and FNet over all frame pairs
         flow_cl = tape["flow_cl"]
@@ -368,15 +339,8 @@ class FRVSRNet(BaseNet):
             else:
                 if kind == "leaky":
                     g = F.prelu_bwd(y, g, slope, torch.empty_like(g), dummy, False)
-                self._wgrad(gbuf, m, x_in, g)
+                pg.conv_wgrad(m, x_in, g, K3, P1)
                 if i > 0:  # the frames need no gradient
                     b_, _, hh, ww, ch = x_in.shape
                     g = F.conv(g, D(m), new(b_, hh, ww, ch), K3, P1)
-        for p, gb in bufs.values():
-            self._grad_done(out, p, gb)
-        return out
-
-    def _wgrad(self, gbuf, conv, x, dy):
-        dw, acc = gbuf(conv.weight)
-        db, _ = gbuf(conv.bias)
-        F.conv_wgrad(x, dy, K3, P1, dw.view(*dw.shape[:2], 1, *dw.shape[2:]), db, accumulate=acc)
+        return pg.done()

@@ -30,8 +30,7 @@ How the step runs:
     block and neighbour.
   * The back-projection differences l0 - x, h0 - x and h0 - h1 are vsrk_sub;
     in the backward the subtrahend receives the negated gradient (0 - g, exact).
-  * The backward pass is an op-level tape, as EDVRNet's: every forward op
-    appends its reverse and the reverses run last to first.  The gradient
+  * The backward pass is an op-level tape (tape.py).  The gradient
     contributions of a tensor with several consumers stay apart until its
     producer takes them; a PReLU backward then adds two of them in its own
     pass (vsrk_prelu_bwd's second gradient operand), so the sum and the
@@ -64,12 +63,7 @@ import torch.nn as nn
 
 from .. import functional as F
 from .base_net import BaseNet
-from .drf_net import K1, K3, P0, P1, _PROJ
-
-
-def _cp(c: int) -> int:
-    """Channels of the storage a c-channel view lives in (whole 16-byte chunks)."""
-    return -(-c // 8) * 8
+from .tape import K1, K3, P0, P1, PROJ, Bwd, cp, empty_view, recorder, subpixel_cache
 
 
 class _ConvBlock(nn.Module):
@@ -125,59 +119,25 @@ class _DBPNet(nn.Module):
         self.output = _ConvBlock(num_stages * feat, feat, 1, 1, 0, act=False)
 
 
-class _Bwd:
-    """State of one reverse pass: the gradient contributions that have arrived
-    per tensor, the parameter gradient buffers and the packed data-gradient
-    weights.  Contributions stay apart until their tensor's producer takes
-    them: a PReLU backward adds two of them in fp32 (one rounding for the sum
-    and the derivative together), and a subtrahend's contribution arrives
-    negated (exact), so that every merge is a sum."""
+class _Bwd(Bwd):
+    """The reverse pass with the packed data-gradient weights pk and the
+    sub-pixel weight cache sp.  A PReLU backward adds two of its output's
+    gradient contributions in fp32 (one rounding for the sum and the
+    derivative together), and a subtrahend's contribution arrives negated
+    (exact), so that every merge is a sum."""
 
-    def __init__(self, net, dev, pk, sp, nonpos, uses, act_of):
-        self.net, self.dev, self.pk, self.sp, self.nonpos = net, dev, pk, sp, nonpos
+    def __init__(self, net, pk, sp, nonpos, uses, act_of):
+        super().__init__(net)
+        self.pk, self.sp, self.nonpos = pk, sp, nonpos
         self.uses, self.act_of = uses, act_of
-        self.G: dict = {}
-        self.bufs: dict = {}
         self.fused: set = set()  # PReLU outputs whose backward ran inside their one consumer's data gradient
         self._zeros: dict = {}
-
-    def new_like(self, t):
-        return torch.empty((*t.shape[:4], _cp(t.shape[4])), dtype=t.dtype, device=self.dev)[..., :t.shape[4]]
-
-    def acc(self, t, g):
-        self.G.setdefault(id(t), []).append(g)
-
-    def take_list(self, t, n):
-        """The contributions to t's gradient, summed down to at most n tensors."""
-        lst = self.G.pop(id(t))
-        while len(lst) > n:
-            b, a = lst.pop(), lst.pop()
-            lst.append(F.add(a, b, self.new_like(a)))
-        return lst
-
-    def take(self, t):
-        return self.take_list(t, 1)[0]
 
     def neg(self, g):
         key = (tuple(g.shape), g.dtype)
         if key not in self._zeros:
             self._zeros[key] = self.new_like(g).zero_()
         return F.sub(self._zeros[key], g, self.new_like(g))
-
-    def route(self, x, parts, gx):
-        if parts is None:
-            self.acc(x, gx)
-        else:
-            for t, lo, hi in parts:
-                self.acc(t, gx[..., lo:hi])
-
-    def gbuf(self, p):
-        """(gradient buffer of p, whether an earlier launch already wrote it)."""
-        ent = self.bufs.get(id(p))
-        if ent is None:
-            self.bufs[id(p)] = (p, self.net._grad_buffer(p))
-            return self.bufs[id(p)][1], False
-        return ent[1], True
 
     def prelu(self, pr, y, pre):
         """The gradient at the input of the PReLU that gave y, and its slope
@@ -188,7 +148,7 @@ class _Bwd:
             return self.take(y)
         gs = self.take_list(y, 2)
         g, g2 = gs[0], (gs[1] if len(gs) > 1 else None)
-        da, seen = self.gbuf(pr.weight)
+        da, seen = self.buf(pr.weight)
         out = self.new_like(g)
         if id(pr) in self.nonpos:
             return F.prelu_bwd(pre(), g, pr.weight, out, da, seen, dy2=g2, pre=True)
@@ -203,31 +163,12 @@ class _Bwd:
         pr = self.act_of.get(id(xx))
         if pr is None or self.uses.get(id(xx)) != 1 or id(pr) in self.nonpos:
             return F.conv(g, wp, out, k, p, **kw)
-        da, seen = self.gbuf(pr.weight)
+        da, seen = self.buf(pr.weight)
         if not F.conv_prelu_bwd(g, wp, out, k, p, xx, pr.weight, da, seen, **kw):
             F.conv(g, wp, out, k, p, mask=xx, mask_slope=pr.weight, **kw)
             F.prelu_wgrad(xx, out, pr.weight, da, seen)
         self.fused.add(id(xx))
         return out
-
-    def wgrad(self, m, x, g, k, p):
-        dw, seen = self.gbuf(m.weight)
-        db, _ = self.gbuf(m.bias)
-        F.conv_wgrad(x, g, k, p, dw.view(*dw.shape[:2], 1, *dw.shape[2:]), db, accumulate=seen)
-
-    def sp_wgrad(self, m, x, g, transposed, proj):
-        k, s, p = proj
-        cop, cip = (s * s * m.out_channels, m.in_channels) if transposed else (m.out_channels, s * s * m.in_channels)
-        dw, seen = self.gbuf(m.weight)
-        db, _ = self.gbuf(m.bias)
-        dweq = torch.empty((cop, cip, 1, 3, 3), dtype=torch.float32, device=self.dev)
-        dbeq = torch.empty(cop, dtype=torch.float32, device=self.dev)
-        code = F.subpixel_code(k, s, p, transposed, False)
-        if transposed:
-            F.conv_wgrad(x, g, K3, P1, dweq, dbeq, dy_shuffle=s, subpixel=code)
-        else:
-            F.conv_wgrad(x, g, K3, P1, dweq, dbeq, x_shuffle=s, subpixel=code)
-        F.subpixel_wgrad_fold(dweq, dbeq, dw, db, k, s, p, transposed, accumulate=seen)
 
 
 class RBPNet(BaseNet):
@@ -236,7 +177,7 @@ class RBPNet(BaseNet):
     def __init__(self, in_channels, out_channels, base_filter, feat, num_stages, num_resblocks, num_frames,
                  upscale_factor):
         super().__init__()
-        if upscale_factor not in _PROJ:
+        if upscale_factor not in PROJ:
             raise ValueError(f"The upscale factor should be 2, 3, 4 or 8. Got {upscale_factor}.")
         if num_stages != 3:
             raise ValueError(f"RBPNet's DBPNet concatenates three back-projection stages: num_stages must be 3, "
@@ -246,7 +187,7 @@ class RBPNet(BaseNet):
         self.num_frames = num_frames
         self.upscale_factor = upscale_factor
         self.t = num_frames // 2 if num_frames % 2 == 1 else num_frames // 2 - 1
-        k, s, p = _PROJ[upscale_factor]
+        k, s, p = PROJ[upscale_factor]
         self.feat0 = _ConvBlock(in_channels, base_filter)
         self.feat1 = _ConvBlock(in_channels * 2, base_filter)
         self.dbp_net = _DBPNet(base_filter, feat, num_stages, k, s, p)
@@ -283,7 +224,7 @@ class RBPNet(BaseNet):
         if len(frames) != self.num_frames:
             raise ValueError(f"RBPNet was built for {self.num_frames} frames, got {len(frames)}")
         cd, f, bf = self.compute_dtype, self.feat, self.base_filter
-        proj = _PROJ[self.upscale_factor]
+        proj = PROJ[self.upscale_factor]
         k, s, p = proj
         x = frames[self.t]
         nbs = frames[:self.t] + frames[self.t + 1:]
@@ -292,8 +233,8 @@ class RBPNet(BaseNet):
         dev = x.device
         PR = F.ACT_PRELU
         pk = self._pack_weights(self._specs(0))
-        ops: list | None = [] if tape is not None else None
-        spc: dict = {}
+        ops, push = recorder(tape is not None)
+        sp = subpixel_cache(cd)
         uses: dict = {}    # id(tensor) -> consumers (a concat consumer counts for its slices)
         act_of: dict = {}  # id(tensor) -> the PReLU that produced it
 
@@ -301,22 +242,8 @@ class RBPNet(BaseNet):
             for t_ in ts:
                 uses[id(t_)] = uses.get(id(t_), 0) + 1
 
-        def sp(m, transposed, mode=0):
-            """(packed sub-pixel image of m's weight, its bias), once per step and mode."""
-            key = id(m.weight)
-            if key not in spc:
-                spc[key] = F.subpixel_conv_weight(m.weight, m.bias, k, s, p, transposed)
-            weq, beq = spc[key]
-            if (key, mode) not in spc:
-                spc[(key, mode)] = F.pack_weight(weq, mode, cd)
-            return spc[(key, mode)], beq
-
         def new(hh, ww, ch, dtype=cd):
-            return torch.empty((B, 1, hh, ww, _cp(ch)), dtype=dtype, device=dev)[..., :ch]
-
-        def push(fn):
-            if ops is not None:
-                ops.append(fn)
+            return empty_view((B, 1, hh, ww), ch, dtype, dev)
 
         def conv(xx, m, y, pr=None, parts=None, need_dx=True):
             """y = [prelu](conv(xx) + bias); parts: the channel slices of xx that are tensors of their own."""
@@ -333,7 +260,7 @@ class RBPNet(BaseNet):
                     g = bk.prelu(pr, y, lambda: F.conv(xx, w0, bk.new_like(y), kk, pp, bias=m.bias))
                 else:
                     g = bk.take(y)
-                bk.wgrad(m, xx, g, kk, pp)
+                bk.conv_wgrad(m, xx, g, kk, pp)
                 if need_dx:
                     bk.route(xx, parts, bk.dgrad(xx, g, bk.pk[(id(m.weight), 1, 1)], kk, pp))
 
@@ -343,7 +270,7 @@ class RBPNet(BaseNet):
         def deconv(xx, blk, y):
             """y = prelu(ConvTranspose2d(k, s, p)(xx)): a 3x3 conv written through the shuffle-s view of y."""
             m, pr = blk.deconv, blk.act
-            wq, bq = sp(m, True)
+            wq, bq = sp(m, proj, True)
             code = F.subpixel_code(k, s, p, True, False)
             F.conv(xx, wq, y, K3, P1, bias=bq, bias_r=1, y_shuffle=s, act=PR, act_param=pr.weight, subpixel=code)
             use(xx)
@@ -352,8 +279,8 @@ class RBPNet(BaseNet):
             def bwd(bk):
                 g = bk.prelu(pr, y, lambda: F.conv(xx, wq, bk.new_like(y), K3, P1, bias=bq, bias_r=1, y_shuffle=s,
                                                    subpixel=code))
-                bk.sp_wgrad(m, xx, g, True, proj)
-                bk.acc(xx, bk.dgrad(xx, g, bk.sp(m, True, 1)[0], K3, P1, x_shuffle=s,
+                bk.subpixel_wgrad(m, xx, g, proj, True, tap_skip=True)
+                bk.acc(xx, bk.dgrad(xx, g, bk.sp(m, proj, True, 1)[0], K3, P1, x_shuffle=s,
                                     subpixel=F.subpixel_code(k, s, p, True, True)))
 
             push(bwd)
@@ -362,7 +289,7 @@ class RBPNet(BaseNet):
         def sconv(xx, blk, y):
             """y = prelu(Conv2d(k, stride s, p)(xx)): a 3x3 conv over the shuffle-s view of xx."""
             m, pr = blk.conv, blk.act
-            wq, bq = sp(m, False)
+            wq, bq = sp(m, proj, False)
             code = F.subpixel_code(k, s, p, False, False)
             F.conv(xx, wq, y, K3, P1, bias=bq, x_shuffle=s, act=PR, act_param=pr.weight, subpixel=code)
             use(xx)
@@ -371,8 +298,8 @@ class RBPNet(BaseNet):
             def bwd(bk):
                 g = bk.prelu(pr, y, lambda: F.conv(xx, wq, bk.new_like(y), K3, P1, bias=bq, x_shuffle=s,
                                                    subpixel=code))
-                bk.sp_wgrad(m, xx, g, False, proj)
-                bk.acc(xx, bk.dgrad(xx, g, bk.sp(m, False, 1)[0], K3, P1, y_shuffle=s,
+                bk.subpixel_wgrad(m, xx, g, proj, False, tap_skip=True)
+                bk.acc(xx, bk.dgrad(xx, g, bk.sp(m, proj, False, 1)[0], K3, P1, y_shuffle=s,
                                     subpixel=F.subpixel_code(k, s, p, False, True)))
 
             push(bwd)
@@ -392,7 +319,7 @@ class RBPNet(BaseNet):
             def bwd(bk):
                 g = bk.prelu(pr, y, lambda: F.conv(t1, w2, bk.new_like(y), K3, P1, bias=m.bias, residual=xx))
                 bk.acc(xx, g)
-                bk.wgrad(m, t1, g, K3, P1)
+                bk.conv_wgrad(m, t1, g, K3, P1)
                 bk.acc(t1, bk.dgrad(t1, g, bk.pk[(id(m.weight), 1, 1)], K3, P1))
 
             push(bwd)
@@ -453,11 +380,11 @@ class RBPNet(BaseNet):
             return xx
 
         xf = x.float()
-        xv = F.to_view(xf, cd, cpad=_cp(C))[..., :C]
+        xv = F.to_view(xf, cd, cpad=cp(C))[..., :C]
         feat_input = conv(xv, self.feat0.conv, new(h, w, bf), self.feat0.act, need_dx=False)
         feat_frame = []
         for nb in nbs:
-            pair = F.to_view(torch.cat([xf, nb.float()], dim=1), cd, cpad=_cp(2 * C))[..., :2 * C]
+            pair = F.to_view(torch.cat([xf, nb.float()], dim=1), cd, cpad=cp(2 * C))[..., :2 * C]
             feat_frame.append(conv(pair, self.feat1.conv, new(h, w, bf), self.feat1.act, need_dx=False))
         nn_ = len(nbs)
         HT = new(H, W, nn_ * f)
@@ -483,16 +410,9 @@ class RBPNet(BaseNet):
     # ------------------------------------------------------------------
     def _backward(self, tape: dict, grads) -> dict:
         g = grads.float()
-        dev = g.device
         host, ev, prelus = tape["slopes"]
         ev.synchronize()
         nonpos = {id(m) for m, a in zip(prelus, host.tolist()) if not a > 0}
         co = self.out_channels
-        bk = _Bwd(self, dev, self._pack_weights(self._specs(1)), tape["sp"], nonpos, tape["uses"], tape["act_of"])
-        bk.acc(tape["yv"], F.to_view(g, self.compute_dtype, cpad=_cp(co))[..., :co])
-        for op in reversed(tape["ops"]):
-            op(bk)
-        out: dict = {}
-        for prm, gb in bk.bufs.values():
-            self._grad_done(out, prm, gb)
-        return out
+        bk = _Bwd(self, self._pack_weights(self._specs(1)), tape["sp"], nonpos, tape["uses"], tape["act_of"])
+        return bk.run(tape["ops"], tape["yv"], F.to_view(g, self.compute_dtype, cpad=cp(co))[..., :co])

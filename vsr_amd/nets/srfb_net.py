@@ -33,13 +33,14 @@ import torch
 import torch.nn as nn
 
 from .. import functional as F
-from .drf_net import _DRFBase, _FBlock, _InBlock, _PROJ, _prelu, K3, P1
+from .drf_net import _DRFBase, _FBlock, _InBlock, _prelu
+from .tape import K3, P1, PROJ
 
 
 class _RBlock(nn.Sequential):
     def __init__(self, in_channels, out_channels, upscale_factor):
         super().__init__()
-        k, s, p = _PROJ[upscale_factor]
+        k, s, p = PROJ[upscale_factor]
         self.add_module("deconv1", nn.ConvTranspose2d(in_channels, in_channels, kernel_size=k, stride=s, padding=p))
         self.add_module("prelu1", _prelu())
         self.add_module("conv2", nn.Conv2d(in_channels, out_channels, kernel_size=3, padding=1))
@@ -75,7 +76,7 @@ class SRFBNet(_DRFBase):
     # ------------------------------------------------------------------
     def _reconstruct(self, t, x, infeat, ffeat, buf, pw, sp):
         f, co = self.num_features, self.out_channels
-        k, s, p = _PROJ[self.upscale_factor]
+        k, s, p = PROJ[self.upscale_factor]
         b, _, h, w, _ = ffeat.shape
         H, W = h * s, w * s
         rb = self.r_block
@@ -106,7 +107,7 @@ class SRFBNet(_DRFBase):
 
     def _reconstruct_backward(self, bk, t, rc, g):
         f = self.num_features
-        k, s, p = _PROJ[self.upscale_factor]
+        k, s, p = PROJ[self.upscale_factor]
         rb = self.r_block
         hr, ffeat = rc["tail_in"], rc["ffeat"]
         b, _, H, W, _ = hr.shape
