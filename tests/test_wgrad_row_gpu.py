@@ -155,6 +155,29 @@ def test_wgrad_row_edsr_upsampler(dt, ci):
     assert (db - db0).abs().max().item() <= 1e-4 * db0.abs().max().item()
 
 
+def test_wgrad_row_edsr_upsampler_accumulate():
+    """The up-sampler form accumulating: dw / db += s * gradient with the
+    output channels permuted by perm_r=2 (gradient accumulation over EDSR's
+    Upsampler conv), against the fp64 gradient of conv2d + pixel_shuffle."""
+    n, h, w, r, ci, s = 2, 11, 37, 2, 64, 0.5
+    co = ci * r * r
+    g = torch.Generator().manual_seed(ci + 5)
+    x = torch.randn((n, 1, h, w, ci), generator=g).to(DEV, torch.bfloat16)
+    gy_hr = torch.randn((n, 1, h * r, w * r, ci), generator=g).to(DEV, torch.bfloat16)
+    base_w = torch.randn((co, ci, 1, 3, 3), generator=g).to(DEV)
+    base_b = torch.randn(co, generator=g).to(DEV)
+    dw, db = base_w.clone(), base_b.clone()
+    F.conv_wgrad(x, gy_hr, (1, 3, 3), (0, 1, 1), dw, db, dy_scale=s, perm_r=r, dy_shuffle=r, accumulate=True)
+    xn = x.double().cpu()[:, 0].permute(0, 3, 1, 2)
+    wr = torch.zeros((co, ci, 3, 3), dtype=torch.float64, requires_grad=True)
+    br = torch.zeros(co, dtype=torch.float64, requires_grad=True)
+    yo = torch.nn.functional.pixel_shuffle(torch.nn.functional.conv2d(xn, wr, br, padding=1), r)
+    yo.backward(gy_hr.double().cpu()[:, 0].permute(0, 3, 1, 2))
+    rw, rb = s * wr.grad.view(co, ci, 1, 3, 3), s * br.grad
+    assert ((dw - base_w).double().cpu() - rw).abs().max().item() <= 1e-4 * rw.abs().max().item()
+    assert ((db - base_b).double().cpu() - rb).abs().max().item() <= 1e-4 * rb.abs().max().item()
+
+
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("r", [2, 3, 4, 8])
 @pytest.mark.parametrize("skip", [False, True])

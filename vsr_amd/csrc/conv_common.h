@@ -1,5 +1,6 @@
 // Shared pieces of the implicit-GEMM convolution kernels (conv_fwd.hip,
-// conv_wgrad.hip).  See conv_fwd.hip for the design notes.
+// conv_wgrad.hip).  See conv_fwd.hip for the design notes; the weight-gradient
+// family's declarations and its slab layout (WgradSlabs) are in conv_wgrad.h.
 #pragma once
 #include "vsrk_common.h"
 #include "vsrk_internal.h"
@@ -178,6 +179,14 @@ __device__ __forceinline__ f32x16 mfma32x16(bf16x8 a, bf16x8 b, f32x16 c) {
 __device__ __forceinline__ f32x16 mfma32x16(f16x8 a, f16x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
+// v_mfma_f32_16x16x32_{bf16,f16}
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f32x4_t mfma16x32(bf16x8 a, bf16x8 b, f32x4_t c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x4_t mfma16x32(f16x8 a, f16x8 b, f32x4_t c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
 
 // 4 consecutive channels of an epilogue tensor, kept packed (uint2 for bf16,
 // uint4 for fp32) between the batched loads and the stores.
@@ -226,23 +235,6 @@ __device__ __forceinline__ void load4(const char* base, int64_t off, bool vec, i
   }
 }
 
-struct WgradArgs {
-  View x, dy;
-  const float* pro_scale;
-  const float* pro_shift;
-  float* ws;
-  int cin, cout;
-  int kd, kh, kw, pd, ph, pw;
-  int prologue, xvec, dyvec;
-  int tiles_h, tiles_w, ntiles, tiles_per_split, nsplit, ncombos, nblk;
-  int n_ci_chunks, n_co_tiles, kd_bias, slab, want_bias, cin_pad;
-  // sub-pixel weight (desc->subpixel): taps with a nonzero weight per
-  // 32-channel block of the shuffled operand (dy: sp_by 1, x: sp_by 2);
-  // the others' gradients are structurally discarded (vsrk_subpixel_wgrad_fold)
-  int sp_by;
-  uint16_t sptap[64];
-};
-
 typedef short v4i16 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
 
@@ -250,8 +242,9 @@ __device__ __forceinline__ v4i16 ds_read_tr(const char* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(p));
 }
 
-// Raw buffer access of the pointwise kernels (conv_pw_impl.h, conv_pw_wide.hip),
-// in a namespace of its own: a kernel file opts in with a using-directive.
+// Raw buffer access (the pointwise, row, rolling and pipelined weight-gradient
+// kernels), in a namespace of its own: a kernel file opts in with a
+// using-directive or using-declarations.
 namespace rawbuf {
 // Raw buffer resource over [base, base + 2 GiB) (wave-uniform base): offsets
 // at or beyond 0x7FFFFFF0 read as zero and drop stores -- the out-of-range
@@ -316,32 +309,6 @@ static inline uint16_t subpixel_tapmask(int32_t code, int r, int sub) {
     }
   return m;
 }
-
-// pipelined 16-bit 3x3(x3) weight gradient (conv_wgrad_pipe.hip): 1 = launched the slab kernel, 0 = not eligible.
-int vsrk_conv_wgrad_pipe(const vsrk_conv::WgradArgs& a, int nco, int nci, int dtype, hipStream_t s);
-// rolling-depth 16-bit Conv3d 3x3x3 weight gradient (conv_wgrad_roll.hip):
-// plan (false = not eligible) and launch (1 = launched the slab kernel, whose
-// slabs wgrad_reduce_kernel sums over 2 * nsplit splits and 3 * nci * nco
-// combos; 0 = not eligible)
-bool vsrk_wgrad_roll_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy, int* nsplit,
-                          int* tps, int* ntiles, int* dzc, size_t* ws_bytes);
-int vsrk_conv_wgrad_roll(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy,
-                         const float* pro_scale, const float* pro_shift, int want_bias, float* ws, size_t ws_bytes,
-                         int* nsplit_out, hipStream_t s);
-// rolling-row 16-bit Conv2d 3x3 weight gradient (conv_wgrad_row.hip): plan
-// (false = not eligible) and launch (1 = launched the slab kernel, whose slabs
-// wgrad_reduce_kernel sums over nsplit splits and ncot * ncic combos of
-// cot_w x 64 channels; 0 = not eligible)
-struct VsrkRowPlan {
-  int bands, band_h, nseg, ncot, ncic, nsplit;
-  int cot_w, slab;  // output channels per combo, floats per slab
-  size_t ws_bytes;
-};
-bool vsrk_wgrad_row_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy, VsrkRowPlan* p);
-int vsrk_conv_wgrad_row(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy, int want_bias,
-                        float* ws, size_t ws_bytes, VsrkRowPlan* plan, hipStream_t s);
-// thin-channel weight gradient (conv_thin.hip): 1 = launched the slab kernel, 0 = not eligible.
-int vsrk_conv_wgrad_thin(const vsrk_conv::WgradArgs& a, int nco, int nci, int perm_r, int dtype, hipStream_t s);
 
 static inline bool view_ok(const vsrk_tensor5* t, const char* what) {
   if (!t || !t->ptr) {

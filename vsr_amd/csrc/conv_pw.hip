@@ -3,6 +3,7 @@
 // points and the two small reduce kernels.  The design notes and the kernels
 // are in conv_pw_impl.h; the conv_pw_*.hip units instantiate them.
 #include "conv_pw_impl.h"
+#include "conv_wgrad.h"
 
 namespace {
 using namespace vsrk_conv;

@@ -157,7 +157,6 @@ using namespace vsrk_conv::rawbuf;
 // no address-space-qualified copy)
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 lds_ld16(uint32_t addr) {
   return __builtin_bit_cast(uint4, *(const __attribute__((address_space(3))) u32x4_t*)(size_t)addr);
 }

@@ -52,20 +52,12 @@
 #endif
 typedef uint32_t roll_u32x4 __attribute__((ext_vector_type(4)));
 typedef int roll_v4i __attribute__((ext_vector_type(4)));
-// Raw buffer resource over [base, base + 2 GiB) (wave-uniform base): offsets
-// at or beyond 0x7FFFFFF0 read as zero and drop stores -- the register-
-// transposed epilogue's out-of-range voxels without branches
-typedef __amdgpu_buffer_rsrc_t RRsrc;
-constexpr uint32_t ROLL_OOB = 0x80000000u;
-__device__ __forceinline__ RRsrc roll_rsrc(const void* base) {
-  const uint64_t b = (uint64_t)base;
-  const uint64_t u = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32)) << 32) |
-                     (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
-  return __builtin_amdgcn_make_buffer_rsrc((void*)u, 0, 0x7FFFFFF0, 0x00020000);
-}
-__device__ __forceinline__ uint4 roll_bload16(RRsrc r, uint32_t off) {
-  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
-}
+// raw buffer access (conv_common.h): the register-transposed epilogue's
+// out-of-range voxels read as zero without branches
+using vsrk_conv::rawbuf::bload16;
+using vsrk_conv::rawbuf::rsrc_at;
+typedef vsrk_conv::rawbuf::Rsrc RRsrc;
+constexpr uint32_t ROLL_OOB = vsrk_conv::rawbuf::OOB;
 // SWAP (2-D forms without a prefetched operand): the flush transposes the
 // accumulators in registers (epilogue_sw) instead of parking them in LDS;
 // measured on the EDSR 64 -> 64 body (profiles/r6_roll_defer_ab.txt, nodefer):
@@ -867,11 +859,11 @@ __global__ __launch_bounds__(RNW * 64, RNW / 4) void conv_roll_kernel(RollArgs a
   const int ecc = 2 * (r >> 4) + hf;
   auto epilogue_sw = [&](const f32x16 (&A)[RMS], const RTile& tl, int dz, int nt, bool use_pre) __attribute__((always_inline)) {
     const int64_t sbase = (int64_t)tl.nb * a.y.sn + (int64_t)dz * a.y.sd;
-    const RRsrc ry = roll_rsrc(reinterpret_cast<const H*>(a.y.ptr) + sbase);
+    const RRsrc ry = rsrc_at(reinterpret_cast<const H*>(a.y.ptr) + sbase);
     // (RE_PMASK: the mask has y's geometry and strides, the host checks)
-    const RRsrc rpm = roll_rsrc(reinterpret_cast<const H*>((EM & RE_PMASK) ? a.msk.ptr : a.y.ptr) + sbase);
-    const RRsrc rmk = roll_rsrc(reinterpret_cast<const H*>(a.msk.ptr) + ((int64_t)tl.nb * a.msk.sn + (int64_t)dz * a.msk.sd));
-    const RRsrc rrs = roll_rsrc(reinterpret_cast<const H*>(a.res.ptr) + ((int64_t)tl.nb * a.res.sn + (int64_t)dz * a.res.sd));
+    const RRsrc rpm = rsrc_at(reinterpret_cast<const H*>((EM & RE_PMASK) ? a.msk.ptr : a.y.ptr) + sbase);
+    const RRsrc rmk = rsrc_at(reinterpret_cast<const H*>(a.msk.ptr) + ((int64_t)tl.nb * a.msk.sn + (int64_t)dz * a.msk.sd));
+    const RRsrc rrs = rsrc_at(reinterpret_cast<const H*>(a.res.ptr) + ((int64_t)tl.nb * a.res.sn + (int64_t)dz * a.res.sd));
     const int co = tl.n0 + nt * 32 + 8 * ecc;
     const int ych = (SP == SP_Y ? a.spoff[(tl.n0 >> 5) + nt] : tl.n0 + nt * 32) + 8 * ecc;
     float bsv[8];
@@ -920,7 +912,7 @@ __global__ __launch_bounds__(RNW * 64, RNW / 4) void conv_roll_kernel(RollArgs a
           float m[8];
           uint4 mv;
           if (PREF && use_pre) mv = __builtin_bit_cast(uint4, pre[PREF ? ms : 0][PREF ? nt : 0][q]);
-          else mv = roll_bload16(rmk, ok ? 2u * (uint32_t)(ho * a.msk.sh + wo * a.msk.sw + co) : ROLL_OOB);
+          else mv = bload16(rmk, ok ? 2u * (uint32_t)(ho * a.msk.sh + wo * a.msk.sw + co) : ROLL_OOB);
           Chunk<H>::unpack(mv, m);
 #pragma unroll
           for (int e = 0; e < 8; ++e) t[e] = m[e] > 0.f ? t[e] : 0.f;
@@ -928,12 +920,12 @@ __global__ __launch_bounds__(RNW * 64, RNW / 4) void conv_roll_kernel(RollArgs a
         if constexpr (EM & RE_PMASK) {
           if constexpr (EM & RE_ACC) {  // the consumer's PReLU backward sees the whole sum: after the accumulate
             float o[8];
-            Chunk<H>::unpack(roll_bload16(ry, yoff), o);
+            Chunk<H>::unpack(bload16(ry, yoff), o);
 #pragma unroll
             for (int e = 0; e < 8; ++e) t[e] += o[e];
           }
           float m[8];
-          Chunk<H>::unpack(roll_bload16(rpm, yoff), m);
+          Chunk<H>::unpack(bload16(rpm, yoff), m);
 #pragma unroll
           for (int e = 0; e < 8; ++e) t[e] = m[e] > 0.f ? t[e] : mslope * t[e];
           float tr[8];
@@ -946,7 +938,7 @@ __global__ __launch_bounds__(RNW * 64, RNW / 4) void conv_roll_kernel(RollArgs a
           float rr[8];
           uint4 rv;
           if (PREF && use_pre) rv = __builtin_bit_cast(uint4, pre[PREF ? ms : 0][PREF ? nt : 0][q]);
-          else rv = roll_bload16(rrs, ok ? 2u * (uint32_t)(ho * a.res.sh + wo * a.res.sw + co) : ROLL_OOB);
+          else rv = bload16(rrs, ok ? 2u * (uint32_t)(ho * a.res.sh + wo * a.res.sw + co) : ROLL_OOB);
           Chunk<H>::unpack(rv, rr);
 #pragma unroll
           for (int e = 0; e < 8; ++e) t[e] += rr[e];
@@ -957,7 +949,7 @@ __global__ __launch_bounds__(RNW * 64, RNW / 4) void conv_roll_kernel(RollArgs a
         }
         if constexpr ((EM & RE_ACC) && !(EM & RE_PMASK)) {
           float o[8];
-          Chunk<H>::unpack(roll_bload16(ry, yoff), o);
+          Chunk<H>::unpack(bload16(ry, yoff), o);
 #pragma unroll
           for (int e = 0; e < 8; ++e) t[e] += o[e];
         }

@@ -79,14 +79,9 @@ constexpr int CR_MINBAND = 4;                  // rows: a band pays 2 halo rows 
 constexpr uint32_t CR_OOB = 0x80000000u;       // buffer offset past the range: loads read zero, stores are dropped
 enum { CE_RES = 1, CE_MASK = 2, CE_ACC = 4, CE_RELU = 8 };
 
-typedef __amdgpu_buffer_rsrc_t CrRsrc;
+typedef rawbuf::Rsrc CrRsrc;
 typedef int cr_v4i __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ CrRsrc cr_rsrc(const void* base) {
-  const uint64_t b = (uint64_t)base;
-  const uint64_t u = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32)) << 32) |
-                     (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
-  return __builtin_amdgcn_make_buffer_rsrc((void*)u, 0, 0x7FFFFFF0, 0x00020000);
-}
+using rawbuf::rsrc_at;
 // byte offset = voff (per lane; CR_OOB: out of range) + soff (wave-uniform,
 // < 2^31: the row and the q-th voxel group, so a lane keeps one offset per view)
 __device__ __forceinline__ uint4 cr_load16(CrRsrc r, uint32_t voff, uint32_t soff) {
@@ -186,10 +181,10 @@ __global__ __launch_bounds__(CR_NW * 64, 1) void conv_row_kernel(ConvRowArgs a) 
     const int r0 = band * a.band_h, r1 = min(r0 + a.band_h, a.H);
     const int nstage = r1 - r0 + 1;  // one per output row, and one for the last flush
 
-    const CrRsrc rx = cr_rsrc(reinterpret_cast<const H*>(a.x.ptr) + (in_ * a.x.sn + id * a.x.sd));
-    const CrRsrc ry = cr_rsrc(reinterpret_cast<const H*>(a.y.ptr) + (in_ * a.y.sn + id * a.y.sd));
-    const CrRsrc rr = cr_rsrc(reinterpret_cast<const H*>(a.res.ptr) + (in_ * a.res.sn + id * a.res.sd));
-    const CrRsrc rm = cr_rsrc(reinterpret_cast<const H*>(a.msk.ptr) + (in_ * a.msk.sn + id * a.msk.sd));
+    const CrRsrc rx = rsrc_at(reinterpret_cast<const H*>(a.x.ptr) + (in_ * a.x.sn + id * a.x.sd));
+    const CrRsrc ry = rsrc_at(reinterpret_cast<const H*>(a.y.ptr) + (in_ * a.y.sn + id * a.y.sd));
+    const CrRsrc rr = rsrc_at(reinterpret_cast<const H*>(a.res.ptr) + (in_ * a.res.sn + id * a.res.sd));
+    const CrRsrc rm = rsrc_at(reinterpret_cast<const H*>(a.msk.ptr) + (in_ * a.msk.sn + id * a.msk.sd));
 
     // per-lane byte offsets inside a row (q = 0; the q-th group's columns go
     // into the uniform offset) and the validity of each group's column

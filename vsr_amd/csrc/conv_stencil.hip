@@ -35,13 +35,6 @@ typedef uint32_t st_u32x4 __attribute__((ext_vector_type(4)));
 #ifndef ST_NT
 #define ST_NT 1  // non-temporal output stores (tail data gradient 681 -> 591 us); 0 for A/B
 #endif
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4_t st_mfma(bf16x8 a, bf16x8 b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4_t st_mfma(f16x8 a, f16x8 b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
 
 struct StArgs {
   const char* x;  // element (n, d, h, w, 0) at x + 2 * (n*xsn + d*xsd + h*xsh + w*xsw)
@@ -248,7 +241,7 @@ __global__ __launch_bounds__(256) void stencil_out_kernel(SoArgs a) {
         f32x4_t c = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
-          c = st_mfma(__builtin_bit_cast(V8, af[ks]), __builtin_bit_cast(V8, xr[j][ks]), c);
+          c = mfma16x32(__builtin_bit_cast(V8, af[ks]), __builtin_bit_cast(V8, xr[j][ks]), c);
         // lane holds P[tap 4 kg + i][voxel 16 b + n16]
 #pragma unroll
         for (int i = 0; i < 4; ++i) {

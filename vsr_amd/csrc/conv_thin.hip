@@ -18,8 +18,7 @@
 // All three are HBM-bound (read the wide side once, write the output once);
 // the MFMAs only keep the arithmetic off the VALU.  Forward epilogue semantics
 // equal conv_fwd's: t = (acc + bias) * out_scale -> act -> mask -> + residual -> + y.
-#include "conv_common.h"
-#include "vsrk_internal.h"
+#include "conv_wgrad.h"
 
 namespace {
 using namespace vsrk_conv;
@@ -728,8 +727,8 @@ int vsrk_conv_fwd_thin(const vsrk_conv_desc* d, const vsrk_tensor5* x, const voi
   return 1;
 }
 
-// Weight gradient of a conv with cout <= 3 (the tail conv F -> 1): same plan
-// (splits x combos, slab size) as vsrk_conv_wgrad, so the reduce is shared.
+// Weight gradient of a conv with cout <= 3 (the tail conv F -> 1): runs on the
+// generic plan and leaves that plan's WgradSlabs (conv_wgrad.hip: wgrad_plan).
 int vsrk_conv_wgrad_thin(const vsrk_conv::WgradArgs& a, int nco, int nci, int perm_r, int dtype, hipStream_t s) {
   if (vsrk_path_mode(VSRK_PATH_THIN) == 0) return 0;
   if (nco != 1 || a.cout > 3 || a.kd != 1 || a.pd != 0 || a.kh != a.kw || a.kh * a.kw * a.cout > 32) return 0;

@@ -1,6 +1,8 @@
 // Implicit-GEMM convolution weight/bias gradient on CDNA4 MFMA (gfx950).
-// Design notes: conv_fwd.hip (layout) and the comment block below.
-#include "conv_common.h"
+// Design notes: conv_fwd.hip (layout) and the comment block below.  This unit
+// holds the generic kernel, its plan and the entry point, which routes between
+// the family's candidates (conv_wgrad.h); the reduce is conv_wgrad_reduce.hip.
+#include "conv_wgrad.h"
 
 namespace {
 using namespace vsrk_conv;
@@ -269,176 +271,48 @@ __global__ __attribute__((amdgpu_waves_per_eu(1, 1))) __launch_bounds__(GTHR) vo
   }
 }
 
-// dw[co][ci][kd][kh][kw] (torch, fp32) = scale * sum_split slab[split][combo][tap][co][ci]
-// (+ dbias from the bias tails).  A block = 64 outputs x 4 split groups; each
-// thread sums a strided quarter of the splits, then the 4 partials are added
-// in a fixed order: deterministic.
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(
-    const float* __restrict__ ws, float* __restrict__ dw, float* __restrict__ db, int nsplit, int ncombos,
-    int slab, int cout, int cin, int kd, int kh, int kw, int nco_t, int nci_t, int cot_w, int cit_w, int kd_bias,
-    int perm_r, float scale, int accumulate) {
-  __shared__ float part[4][64];
-  const int taps2 = kh * kw;
-  const int64_t nw = (int64_t)cout * cin * kd * taps2;
-  const int64_t idx = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
-  const int grp = threadIdx.x >> 6;
-  const int64_t total = nw + (db ? cout : 0);
-  const int64_t sstride = (int64_t)ncombos * slab;
-  const float* p = nullptr;
-  int co = 0, ci = 0, tap = 0, kdi = 0;
-  if (idx < nw) {
-    ci = idx % cin;
-    int64_t t = idx / cin;
-    co = t % cout;
-    t /= cout;
-    tap = t % taps2;
-    kdi = t / taps2;
-    const int combo = (kdi * nci_t + ci / cit_w) * nco_t + co / cot_w;
-    p = ws + (int64_t)combo * slab + ((int64_t)tap * cot_w + (co % cot_w)) * cit_w + (ci % cit_w);
-  } else if (idx < total) {
-    co = (int)(idx - nw);
-    const int combo = (kd_bias * nci_t + 0) * nco_t + co / cot_w;
-    p = ws + (int64_t)combo * slab + (int64_t)taps2 * cot_w * cit_w + (co % cot_w);
-  }
-  float s = 0.f;
-  if (p) {
-    int k = grp;
-    for (; k + 12 < nsplit; k += 16) {
-      const float a0 = p[k * sstride], a1 = p[(k + 4) * sstride], a2 = p[(k + 8) * sstride],
-                  a3 = p[(k + 12) * sstride];
-      s += a0;
-      s += a1;
-      s += a2;
-      s += a3;
-    }
-    for (; k < nsplit; k += 4) s += p[k * sstride];
-  }
-  part[grp][threadIdx.x & 63] = s;
-  __syncthreads();
-  if (grp != 0 || idx >= total) return;
-  const int l = threadIdx.x;
-  s = ((part[0][l] + part[1][l]) + part[2][l]) + part[3][l];
-  int cot = co;
-  if (perm_r > 1) {
-    const int rr = perm_r * perm_r, cp = cout / rr;
-    const int sub = co / cp, cc = co - sub * cp;
-    cot = cc * rr + sub;
-  }
-  s *= scale;
-  if (idx < nw) {
-    const int khi = tap / kw, kwi = tap % kw;
-    float* d = dw + ((((int64_t)cot * cin + ci) * kd + kdi) * kh + khi) * kw + kwi;
-    *d = accumulate ? *d + s : s;
-  } else {
-    db[cot] = accumulate ? db[cot] + s : s;
-  }
-}
-
-// The same sums as wgrad_reduce_kernel, in dw's memory order: a workgroup
-// owns one (output channel, input block of cit_w channels, kd) and its
-// cit_w x taps outputs, reads each split's [tap][ci] rows of the slab
-// coalesced (8 splits of loads in flight per output), sums the splits in
-// order 0, 1, 2, ... in fp32, and writes the (ci, tap) run of dw through LDS.
-// Workgroups past the weights sum the dbias tails, one output channel per
-// lane.  (wgrad_reduce_kernel writes dw with a 9-float stride per lane: the
-// DRF sub-pixel weight gradients spent ~27 us per reduce in it.)
-__global__ __launch_bounds__(256) void wgrad_reduce_rows_kernel(
-    const float* __restrict__ ws, float* __restrict__ dw, float* __restrict__ db, int nsplit, int slab, int cout,
-    int cin, int kd, int taps2, int nco_t, int nci_t, int cot_w, int cit_w, int kd_bias, int perm_r, float scale,
-    int accumulate, int nblk_w) {
-  constexpr int U = 8;
-  __shared__ float out[64 * 9];
-  const int64_t sstride = (int64_t)nco_t * nci_t * kd * slab;
-  const int tid = threadIdx.x;
-  auto sum_splits = [&](const float* p) __attribute__((always_inline)) {
-    float s = 0.f;
-    for (int k0 = 0; k0 < nsplit; k0 += U) {
-      float v[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) v[u] = k0 + u < nsplit ? p[(int64_t)(k0 + u) * sstride] : 0.f;
-#pragma unroll
-      for (int u = 0; u < U; ++u) s += v[u];
-    }
-    return s;
-  };
-  auto torch_co = [&](int co) __attribute__((always_inline)) {
-    if (perm_r > 1) {
-      const int rr = perm_r * perm_r, cp = cout / rr;
-      const int sub = co / cp;
-      return (co - sub * cp) * rr + sub;
-    }
-    return co;
-  };
-  if ((int)blockIdx.x >= nblk_w) {  // dbias
-    if (!db) return;
-    const int co = ((int)blockIdx.x - nblk_w) * 256 + tid;
-    if (co >= cout) return;
-    const int combo = (kd_bias * nci_t + 0) * nco_t + co / cot_w;
-    const float s = sum_splits(ws + (int64_t)combo * slab + (int64_t)taps2 * cot_w * cit_w + (co % cot_w)) * scale;
-    const int cot = torch_co(co);
-    db[cot] = accumulate ? db[cot] + s : s;
-    return;
-  }
-  int b = blockIdx.x;
-  const int kdi = b % kd;
-  b /= kd;
-  const int cic = b % nci_t;
-  const int co = b / nci_t;
-  const int ci0 = cic * cit_w;
-  const int nci = min(cit_w, cin - ci0);
-  const int nout = nci * taps2;
-  const int combo = (kdi * nci_t + cic) * nco_t + co / cot_w;
-  const float* base = ws + (int64_t)combo * slab + (int64_t)(co % cot_w) * cit_w;
-  for (int j = tid; j < cit_w * taps2; j += 256) {  // read order: tap-major rows of cit_w input channels
-    const int tap = j / cit_w, cil = j - tap * cit_w;
-    if (cil < nci) out[cil * taps2 + tap] = sum_splits(base + (int64_t)tap * cot_w * cit_w + cil) * scale;
-  }
-  __syncthreads();
-  float* d = dw + ((int64_t)torch_co(co) * cin + ci0) * kd * taps2 + (int64_t)kdi * taps2;
-  for (int j = tid; j < nout; j += 256) {  // dw order: (ci, [kd,] tap)
-    const int cil = j / taps2, tap = j - cil * taps2;
-    float* q = d + (int64_t)cil * kd * taps2 + tap;
-    *q = accumulate ? *q + out[j] : out[j];
-  }
-}
-
-// A/B knobs, read at load
-const int g_wgrad_reduce = vsrk_env_flag("VSRK_WGRAD_REDUCE", 1);  // 0 keeps the per-output reduce kernel
-// VSRK_WGRAD_TARGET=<workgroups> (at least 64) overrides wgrad_plan's split rule; unset or 0: the rule
+// VSRK_WGRAD_TARGET=<workgroups> (at least 64) overrides wgrad_plan's split rule (A/B, read at load); unset or 0: the rule
 const int g_wgrad_target_env = vsrk_env_int("VSRK_WGRAD_TARGET", 0);
 const int g_wgrad_target = g_wgrad_target_env ? std::max(64, g_wgrad_target_env) : 0;
 
-// the row-order reduce where it fits; VSRK_WGRAD_REDUCE=0 keeps the per-output kernel (A/B)
-static bool wgrad_reduce_rows(const float* ws, float* dw, float* db, int nsplit, int slab, int cout, int cin, int kd,
-                              int taps2, int nco_t, int nci_t, int cot_w, int cit_w, int kd_bias, int perm_r,
-                              float scale, int accumulate, hipStream_t s) {
-  const int nblk_w = cout * nci_t * kd;
-  // one lane sums all splits of an output: only for few splits and enough
-  // workgroups (EDSR's 64 -> 64 has 256 splits over 64 such workgroups)
-  if (!g_wgrad_reduce || cit_w * taps2 > 64 * 9 || nsplit > 32 || nblk_w < 256) return false;
-  const int nblk_b = db ? (int)ceil_div64(cout, 256) : 0;
-  wgrad_reduce_rows_kernel<<<nblk_w + nblk_b, 256, 0, s>>>(ws, dw, db, nsplit, slab, cout, cin, kd, taps2, nco_t,
-                                                            nci_t, cot_w, cit_w, kd_bias, perm_r, scale, accumulate,
-                                                            nblk_w);
-  return true;
+template <typename T, int NCO, int NCI, int KK, bool VEC>
+void launch_wgrad(const WgradArgs& a, hipStream_t s) {
+  constexpr int PB = 32 * (int)sizeof(T);
+  constexpr int SLOTS = (GTH + KK - 1) * (TW + KK - 1);
+  const size_t stage = (size_t)(NCO * GTH * TW + NCI * SLOTS) * PB + (a.prologue ? 2 * a.cin_pad * 4 : 0);
+  const size_t red = (4 / (NCO * NCI)) > 1 ? (size_t)NCO * NCI * KK * KK * 1024 * sizeof(float) : 0;
+  const size_t bias = (size_t)GTHR * (16 / sizeof(T)) * sizeof(float);
+  const size_t lds = std::max(stage, std::max(red, bias));
+  auto kern = conv_wgrad_kernel<T, NCO, NCI, KK, VEC>;
+  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  kern<<<a.nblk, GTHR, lds, s>>>(a);
 }
 
-}  // namespace
+template <typename T, int NCO, int NCI>
+void wgrad_k(const WgradArgs& a, bool vec, hipStream_t s) {
+  if (a.kh == 1) {
+    if (vec) launch_wgrad<T, NCO, NCI, 1, true>(a, s); else launch_wgrad<T, NCO, NCI, 1, false>(a, s);
+  } else {
+    if (vec) launch_wgrad<T, NCO, NCI, 3, true>(a, s); else launch_wgrad<T, NCO, NCI, 3, false>(a, s);
+  }
+}
+
+// The generic plan: the thin, pipelined and generic kernels run on it.
 struct WgradPlan {
-  int nco, nci;            // channel blocks per workgroup (x32)
-  int n_co_tiles, n_ci_chunks, ncombos;
-  int ntiles, tps, nsplit, slab;
-  size_t ws_bytes;
+  int nco, nci;  // channel blocks per workgroup (x32)
+  int ncombos, ntiles, tps;
+  WgradSlabs slabs;
 };
 
-static WgradPlan wgrad_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy) {
+WgradPlan wgrad_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy) {
   WgradPlan p;
+  WgradSlabs& sl = p.slabs;
   const bool f32 = x->dtype == VSRK_F32;
   p.nco = (!f32 && dy->c > 32) ? 2 : 1;
   p.nci = (!f32 && x->c > 32) ? 2 : 1;
-  p.n_co_tiles = ceil_div(dy->c, 32 * p.nco);
-  p.n_ci_chunks = ceil_div(x->c, 32 * p.nci);
-  p.ncombos = p.n_co_tiles * p.n_ci_chunks * d->kd;
+  sl.nco_t = ceil_div(dy->c, 32 * p.nco);
+  sl.nci_t = ceil_div(x->c, 32 * p.nci);
+  p.ncombos = sl.nco_t * sl.nci_t * d->kd;
   p.ntiles = dy->n * dy->d * ceil_div(dy->h, GTH) * ceil_div(dy->w, TW);
   // Splits (workgroups per combo): about 512 workgroups (two resident per
   // CU), but no fewer than 16 tiles (of 8x32 voxels) per workgroup while that
@@ -460,145 +334,27 @@ static WgradPlan wgrad_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, cons
   if (vsrk_g_grid_cap > 0) want = std::max(1, vsrk_g_grid_cap / p.ncombos);
   want = std::max(1, std::min(want, p.ntiles));
   p.tps = ceil_div(p.ntiles, want);
-  p.nsplit = ceil_div(p.ntiles, p.tps);
-  p.slab = d->kh * d->kw * 1024 * p.nco * p.nci + 32 * p.nco;
-  p.ws_bytes = (size_t)p.nsplit * p.ncombos * p.slab * sizeof(float);
+  // the kernels' slabs (the end of conv_wgrad_kernel): split-major, one per
+  // (split, combo) of 32 * nco x 32 * nci channels and a kd tap
+  sl.nsplit = ceil_div(p.ntiles, p.tps);
+  sl.slab = d->kh * d->kw * 1024 * p.nco * p.nci + 32 * p.nco;
+  sl.kd = d->kd; sl.kh = d->kh; sl.kw = d->kw;
+  sl.cot_w = 32 * p.nco; sl.cit_w = 32 * p.nci;
+  sl.kd_bias = std::min(d->pd, d->kd - 1);
+  sl.rows_ok = true;
   return p;
 }
 
-// Views spanning more than the rolling weight gradient's 32-bit element
-// offsets (DUF's concat buffer at cfg 5) run in sample chunks that fit: the
-// chunk's sample count, 0 when no split applies
-static int wgrad_roll_chunk(const vsrk_tensor5* x, const vsrk_tensor5* dy) {
-  auto fits = [&](int64_t n) {
-    for (const vsrk_tensor5* t : {x, dy})
-      if (n * t->sn + (int64_t)t->d * t->sd + (int64_t)(t->h + 64) * t->sh + (int64_t)(t->w + 64) * t->sw + t->c >=
-          (1ll << 31))
-        return false;
-    return true;
-  };
-  if (x->n <= 1 || x->n != dy->n || x->sn < 0 || dy->sn < 0 || fits(x->n)) return 0;
-  int nc = x->n;
-  while (nc > 1 && !fits(nc)) nc = (nc + 1) / 2;
-  return fits(nc) ? nc : 0;
-}
-
-extern "C" size_t vsrk_conv_wgrad_workspace_size(const vsrk_conv_desc* d, const vsrk_tensor5* x,
-                                                 const vsrk_tensor5* dy) {
-  int ns, tps, nt, dzc;
-  size_t roll = 0;
-  if (!vsrk_wgrad_roll_plan(d, x, dy, &ns, &tps, &nt, &dzc, &roll)) {
-    roll = 0;
-    if (const int nc = wgrad_roll_chunk(x, dy)) {  // the sample chunks' plan
-      vsrk_tensor5 xc = *x, gc = *dy;
-      xc.n = gc.n = nc;
-      if (!vsrk_wgrad_roll_plan(d, &xc, &gc, &ns, &tps, &nt, &dzc, &roll)) roll = 0;
-    }
-  }
-  VsrkRowPlan rp;
-  const size_t row = vsrk_wgrad_row_plan(d, x, dy, &rp) ? rp.ws_bytes : 0;
-  return std::max(std::max(std::max(wgrad_plan(d, x, dy).ws_bytes, vsrk_conv_wgrad_pw_workspace(d, x, dy)), roll), row);
-}
-
-template <typename T, int NCO, int NCI, int KK, bool VEC>
-static void launch_wgrad(const WgradArgs& a, hipStream_t s) {
-  constexpr int PB = 32 * (int)sizeof(T);
-  constexpr int SLOTS = (GTH + KK - 1) * (TW + KK - 1);
-  const size_t stage = (size_t)(NCO * GTH * TW + NCI * SLOTS) * PB + (a.prologue ? 2 * a.cin_pad * 4 : 0);
-  const size_t red = (4 / (NCO * NCI)) > 1 ? (size_t)NCO * NCI * KK * KK * 1024 * sizeof(float) : 0;
-  const size_t bias = (size_t)GTHR * (16 / sizeof(T)) * sizeof(float);
-  const size_t lds = std::max(stage, std::max(red, bias));
-  auto kern = conv_wgrad_kernel<T, NCO, NCI, KK, VEC>;
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  kern<<<a.nblk, GTHR, lds, s>>>(a);
-}
-
-template <typename T, int NCO, int NCI>
-static void wgrad_k(const WgradArgs& a, bool vec, hipStream_t s) {
-  if (a.kh == 1) {
-    if (vec) launch_wgrad<T, NCO, NCI, 1, true>(a, s); else launch_wgrad<T, NCO, NCI, 1, false>(a, s);
-  } else {
-    if (vec) launch_wgrad<T, NCO, NCI, 3, true>(a, s); else launch_wgrad<T, NCO, NCI, 3, false>(a, s);
-  }
-}
-
-extern "C" int vsrk_conv_wgrad(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy,
-                               const float* pro_scale, const float* pro_shift, float dy_scale, int32_t perm_r,
-                               float* dw, float* dbias, int32_t accumulate, void* workspace,
-                               size_t workspace_bytes, void* stream) {
-  VSRK_CHECK(d && x && dy && dw, "conv_wgrad: null argument");
-  VSRK_CHECK(x->dtype == dy->dtype, "conv_wgrad: x/dy dtype mismatch");
+// Launches the plan's slab kernel: thin, else pipelined, else generic.
+int wgrad_generic(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy, const float* pro_scale,
+                  const float* pro_shift, int perm_r, bool want_bias, float* ws, const WgradPlan& p, hipStream_t s) {
   const int es = vsrk_esize(x->dtype);
-  if (!view_ok(x, "conv_wgrad x") || !view_ok(dy, "conv_wgrad dy")) return VSRK_ERR_INVALID;
-  VSRK_CHECK(d->kh == d->kw && (d->kh == 1 || d->kh == 3), "conv_wgrad: kh = kw in {1, 3}");
-  VSRK_CHECK(!(d->prologue & VSRK_PRO_AFFINE) || (pro_scale && pro_shift), "conv_wgrad: affine prologue needs scale/shift");
-  hipStream_t s = (hipStream_t)stream;
-  const int pw = vsrk_conv_wgrad_pw(d, x, dy, pro_scale, pro_shift, dy_scale, perm_r, dw, dbias, accumulate,
-                                    workspace, workspace_bytes, s);
-  if (pw != 0) return pw > 0 ? VSRK_OK : -pw;
-  if (workspace && dy->n * dy->d * dy->h * dy->w > 0) {
-    // rolling-depth 3x3x3 kernel (conv_wgrad_roll.hip): its slabs, the same reduce
-    auto roll = [&](const vsrk_tensor5* xv, const vsrk_tensor5* gv, int32_t acc) -> bool {
-      int ns = 0;
-      if (!vsrk_conv_wgrad_roll(d, xv, gv, pro_scale, pro_shift, dbias != nullptr, (float*)workspace, workspace_bytes,
-                                &ns, s))
-        return false;
-      const int nci = x->c / 32, nco = dy->c / 32;
-      const int64_t total = (int64_t)dy->c * x->c * 27 + (dbias ? dy->c : 0);
-      if (!wgrad_reduce_rows((const float*)workspace, dw, dbias, 2 * ns, 9 * 1024 + 32, dy->c, x->c, 3, 9, nco, nci,
-                             32, 32, std::min(d->pd, 2), perm_r, dy_scale, acc, s))
-        wgrad_reduce_kernel<<<(int)ceil_div64(total, 64), 256, 0, s>>>(
-            (const float*)workspace, dw, dbias, 2 * ns, 3 * nci * nco, 9 * 1024 + 32, dy->c, x->c, 3, 3, 3, nco, nci,
-            32, 32, std::min(d->pd, 2), perm_r, dy_scale, acc);
-      return true;
-    };
-    if (roll(x, dy, accumulate)) {
-      VSRK_LAUNCH_CHECK("conv_wgrad(roll)");
-      return VSRK_OK;
-    }
-    // views spanning more than the kernel's 32-bit element offsets (DUF's
-    // concat buffer at cfg 5): sample chunks that fit, each reduced onto dw
-    // after the first (fixed chunk order: deterministic)
-    if (const int nc = wgrad_roll_chunk(x, dy)) {
-      bool ok = true;
-      for (int n0 = 0; ok && n0 < x->n; n0 += nc) {
-        vsrk_tensor5 xc = *x, gc = *dy;
-        xc.n = gc.n = std::min(nc, x->n - n0);
-        xc.ptr = (char*)x->ptr + (int64_t)n0 * x->sn * es;
-        gc.ptr = (char*)dy->ptr + (int64_t)n0 * dy->sn * es;
-        if (!roll(&xc, &gc, n0 == 0 ? accumulate : 1)) {
-          VSRK_CHECK(n0 == 0, "conv_wgrad(roll): a sample chunk was not eligible");
-          ok = false;  // nothing launched: the other paths below
-        }
-      }
-      if (ok) {
-        VSRK_LAUNCH_CHECK("conv_wgrad(roll, sample chunks)");
-        return VSRK_OK;
-      }
-    }
-  }
-  if (workspace && dy->n * dy->d * dy->h * dy->w > 0) {
-    // rolling-row Conv2d 3x3 kernel (conv_wgrad_row.hip): 32 x 64 channel slabs
-    VsrkRowPlan rp;
-    if (vsrk_conv_wgrad_row(d, x, dy, dbias != nullptr, (float*)workspace, workspace_bytes, &rp, s)) {
-      VSRK_LAUNCH_CHECK("conv_wgrad(row)");
-      const int64_t total = (int64_t)dy->c * x->c * 9 + (dbias ? dy->c : 0);
-      wgrad_reduce_kernel<<<(int)ceil_div64(total, 64), 256, 0, s>>>(
-          (const float*)workspace, dw, dbias, rp.nsplit, rp.ncot * rp.ncic, rp.slab, dy->c, x->c, 1, 3, 3,
-          rp.ncot, rp.ncic, rp.cot_w, 64, 0, perm_r, dy_scale, accumulate);
-      VSRK_LAUNCH_CHECK("conv_wgrad_reduce");
-      return VSRK_OK;
-    }
-  }
-  const WgradPlan p = wgrad_plan(d, x, dy);
-  VSRK_CHECK(workspace && workspace_bytes >= p.ws_bytes, "conv_wgrad: workspace %zu < %zu bytes", workspace_bytes,
-             p.ws_bytes);
   WgradArgs a;
   a.x = make_view(x);
   a.dy = make_view(dy);
   a.pro_scale = pro_scale;
   a.pro_shift = pro_shift;
-  a.ws = (float*)workspace;
+  a.ws = ws;
   a.cin = x->c;
   a.cout = dy->c;
   a.kd = d->kd; a.kh = d->kh; a.kw = d->kw;
@@ -610,14 +366,14 @@ extern "C" int vsrk_conv_wgrad(const vsrk_conv_desc* d, const vsrk_tensor5* x, c
   a.tiles_w = ceil_div(dy->w, TW);
   a.ntiles = p.ntiles;
   a.tiles_per_split = p.tps;
-  a.nsplit = p.nsplit;
+  a.nsplit = p.slabs.nsplit;
   a.ncombos = p.ncombos;
-  a.nblk = p.nsplit * p.ncombos;
-  a.n_ci_chunks = p.n_ci_chunks;
-  a.n_co_tiles = p.n_co_tiles;
-  a.kd_bias = std::min(d->pd, d->kd - 1);
-  a.slab = p.slab;
-  a.want_bias = dbias != nullptr;
+  a.nblk = p.slabs.nsplit * p.ncombos;
+  a.n_ci_chunks = p.slabs.nci_t;
+  a.n_co_tiles = p.slabs.nco_t;
+  a.kd_bias = p.slabs.kd_bias;
+  a.slab = p.slabs.slab;
+  a.want_bias = want_bias;
   a.cin_pad = round_up(x->c, 32 * p.nci);
   a.sp_by = 0;
   if (d->subpixel && d->kd == 1 && d->kh == 3 && d->kw == 3 && ((x->shuffle > 1) != (dy->shuffle > 1))) {
@@ -629,12 +385,11 @@ extern "C" int vsrk_conv_wgrad(const vsrk_conv_desc* d, const vsrk_tensor5* x, c
       for (int b = 0; b < t->c / 32; ++b) a.sptap[b] = subpixel_tapmask(code, r, b * 32 / cph);
     }
   }
-  if (p.ntiles == 0) return VSRK_OK;
   const bool vec = a.xvec && a.dyvec;
   if (vsrk_is16(x->dtype) && vsrk_conv_wgrad_thin(a, p.nco, p.nci, perm_r, x->dtype, s)) {
-    // thin-channel kernel (conv_thin.hip), same slab layout
+    // thin-channel kernel (conv_thin.hip)
   } else if (vsrk_is16(x->dtype) && vsrk_conv_wgrad_pipe(a, p.nco, p.nci, x->dtype, s)) {
-    // two-stage pipelined kernel (conv_wgrad_pipe.hip), same slab layout
+    // two-stage pipelined kernel (conv_wgrad_pipe.hip)
   } else if (vsrk_is16(x->dtype)) {
     vsrk_dispatch16(x->dtype, [&](auto tag) {
       using H = decltype(tag);
@@ -648,13 +403,136 @@ extern "C" int vsrk_conv_wgrad(const vsrk_conv_desc* d, const vsrk_tensor5* x, c
     wgrad_k<float, 1, 1>(a, vec, s);
   }
   VSRK_LAUNCH_CHECK("conv_wgrad");
-  const int64_t total = (int64_t)dy->c * x->c * d->kd * d->kh * d->kw + (dbias ? dy->c : 0);
-  if (!wgrad_reduce_rows((const float*)workspace, dw, dbias, p.nsplit, p.slab, dy->c, x->c, d->kd, d->kh * d->kw,
-                         p.n_co_tiles, p.n_ci_chunks, 32 * p.nco, 32 * p.nci, a.kd_bias, perm_r, dy_scale, accumulate,
-                         s))
-    wgrad_reduce_kernel<<<(int)ceil_div64(total, 64), 256, 0, s>>>(
-        (const float*)workspace, dw, dbias, p.nsplit, p.ncombos, p.slab, dy->c, x->c, d->kd, d->kh, d->kw,
-        p.n_co_tiles, p.n_ci_chunks, 32 * p.nco, 32 * p.nci, a.kd_bias, perm_r, dy_scale, accumulate);
-  VSRK_LAUNCH_CHECK("conv_wgrad_reduce");
   return VSRK_OK;
+}
+
+// Views spanning more than the rolling weight gradient's 32-bit element
+// offsets (DUF's concat buffer at cfg 5) run in sample chunks that fit: the
+// chunk's sample count, 0 when no split applies
+int wgrad_roll_chunk(const vsrk_tensor5* x, const vsrk_tensor5* dy) {
+  auto fits = [&](int64_t n) {
+    for (const vsrk_tensor5* t : {x, dy})
+      if (n * t->sn + (int64_t)t->d * t->sd + (int64_t)(t->h + 64) * t->sh + (int64_t)(t->w + 64) * t->sw + t->c >=
+          (1ll << 31))
+        return false;
+    return true;
+  };
+  if (x->n <= 1 || x->n != dy->n || x->sn < 0 || dy->sn < 0 || fits(x->n)) return 0;
+  int nc = x->n;
+  while (nc > 1 && !fits(nc)) nc = (nc + 1) / 2;
+  return fits(nc) ? nc : 0;
+}
+
+// The candidates, in routing order.  Each answers a request with "not
+// eligible" or a plan; the answer never depends on the workspace.
+enum WgradKind { WG_PW, WG_ROLL, WG_ROLL_CHUNKS, WG_ROW, WG_GENERIC, WG_COUNT };
+struct WgradCand {
+  size_t ws_bytes;
+  int chunk_n;        // WG_ROLL_CHUNKS: samples per chunk
+  VsrkRollPlan roll;  // WG_ROLL; WG_ROLL_CHUNKS: the plan of a full chunk
+  VsrkRowPlan row;
+  WgradPlan gen;
+};
+
+bool wgrad_candidate(int kind, const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy, WgradCand* c) {
+  switch (kind) {
+    case WG_PW:  // (its own slabs and reduce: conv_pw.hip)
+      c->ws_bytes = vsrk_conv_wgrad_pw_workspace(d, x, dy);
+      return c->ws_bytes != 0;
+    case WG_ROLL:
+      if (!vsrk_wgrad_roll_plan(d, x, dy, &c->roll)) return false;
+      c->ws_bytes = c->roll.slabs.ws_bytes();
+      return true;
+    case WG_ROLL_CHUNKS: {  // only views the whole-view form refuses
+      vsrk_tensor5 xc = *x, gc = *dy;
+      xc.n = gc.n = c->chunk_n = wgrad_roll_chunk(x, dy);
+      if (!c->chunk_n || vsrk_wgrad_roll_plan(d, x, dy, &c->roll) || !vsrk_wgrad_roll_plan(d, &xc, &gc, &c->roll))
+        return false;
+      c->ws_bytes = c->roll.slabs.ws_bytes();
+      return true;
+    }
+    case WG_ROW:
+      if (!vsrk_wgrad_row_plan(d, x, dy, &c->row)) return false;
+      c->ws_bytes = c->row.slabs.ws_bytes();
+      return true;
+    default:  // WG_GENERIC: always eligible
+      c->gen = wgrad_plan(d, x, dy);
+      c->ws_bytes = c->gen.slabs.ws_bytes();
+      return true;
+  }
+}
+
+}  // namespace
+
+extern "C" size_t vsrk_conv_wgrad_workspace_size(const vsrk_conv_desc* d, const vsrk_tensor5* x,
+                                                 const vsrk_tensor5* dy) {
+  size_t need = 0;
+  WgradCand c;
+  for (int kind = 0; kind < WG_COUNT; ++kind)
+    if (wgrad_candidate(kind, d, x, dy, &c)) need = std::max(need, c.ws_bytes);
+  return need;
+}
+
+extern "C" int vsrk_conv_wgrad(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy,
+                               const float* pro_scale, const float* pro_shift, float dy_scale, int32_t perm_r,
+                               float* dw, float* dbias, int32_t accumulate, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+  VSRK_CHECK(d && x && dy && dw, "conv_wgrad: null argument");
+  VSRK_CHECK(x->dtype == dy->dtype, "conv_wgrad: x/dy dtype mismatch");
+  if (!view_ok(x, "conv_wgrad x") || !view_ok(dy, "conv_wgrad dy")) return VSRK_ERR_INVALID;
+  VSRK_CHECK(d->kh == d->kw && (d->kh == 1 || d->kh == 3), "conv_wgrad: kh = kw in {1, 3}");
+  VSRK_CHECK(!(d->prologue & VSRK_PRO_AFFINE) || (pro_scale && pro_shift), "conv_wgrad: affine prologue needs scale/shift");
+  hipStream_t s = (hipStream_t)stream;
+  float* ws = (float*)workspace;
+  // The first eligible candidate runs.  The pointwise kernel has no output
+  // permutation; the rolling kernels want voxels and a workspace (without:
+  // the generic path's checks).
+  const bool rolling = workspace && dy->n * dy->d * dy->h * dy->w > 0;
+  WgradCand c;
+  int kind = WG_PW;
+  for (;; ++kind) {
+    if (kind == WG_PW && perm_r > 1) continue;
+    if ((kind == WG_ROLL || kind == WG_ROLL_CHUNKS || kind == WG_ROW) && !rolling) continue;
+    if (wgrad_candidate(kind, d, x, dy, &c)) break;  // WG_GENERIC always is
+  }
+  VSRK_CHECK(workspace && workspace_bytes >= c.ws_bytes, "conv_wgrad: workspace %zu < %zu bytes", workspace_bytes,
+             c.ws_bytes);
+  auto roll = [&](const vsrk_tensor5* xv, const vsrk_tensor5* gv, const VsrkRollPlan& p, int32_t acc) -> int {
+    vsrk_conv_wgrad_roll(d, xv, gv, pro_scale, pro_shift, dbias != nullptr, ws, p, s);
+    VSRK_LAUNCH_CHECK("conv_wgrad(roll)");
+    return wgrad_reduce(p.slabs, ws, dy->c, x->c, perm_r, dy_scale, acc, dw, dbias, s);
+  };
+  switch (kind) {
+    case WG_PW: {
+      const int pw = vsrk_conv_wgrad_pw(d, x, dy, pro_scale, pro_shift, dy_scale, perm_r, dw, dbias, accumulate,
+                                        workspace, workspace_bytes, s);
+      VSRK_CHECK(pw != 0, "conv_wgrad(pw): planned but not launched");
+      return pw > 0 ? VSRK_OK : -pw;
+    }
+    case WG_ROLL:
+      return roll(x, dy, c.roll, accumulate);
+    case WG_ROLL_CHUNKS:  // each chunk reduced onto dw after the first (fixed chunk order: deterministic)
+      for (int n0 = 0, es = vsrk_esize(x->dtype); n0 < x->n; n0 += c.chunk_n) {
+        vsrk_tensor5 xc = *x, gc = *dy;
+        xc.n = gc.n = std::min(c.chunk_n, x->n - n0);
+        xc.ptr = (char*)x->ptr + (int64_t)n0 * x->sn * es;
+        gc.ptr = (char*)dy->ptr + (int64_t)n0 * dy->sn * es;
+        VsrkRollPlan p = c.roll;
+        bool ok = true;
+        if (xc.n != c.chunk_n) ok = vsrk_wgrad_roll_plan(d, &xc, &gc, &p);  // the short last chunk: its own plan
+        VSRK_CHECK(ok && p.slabs.ws_bytes() <= workspace_bytes, "conv_wgrad(roll): a sample chunk was not eligible");
+        const int st = roll(&xc, &gc, p, n0 == 0 ? accumulate : 1);
+        if (st != VSRK_OK) return st;
+      }
+      return VSRK_OK;
+    case WG_ROW:
+      vsrk_conv_wgrad_row(d, x, dy, dbias != nullptr, ws, c.row, s);
+      VSRK_LAUNCH_CHECK("conv_wgrad(row)");
+      return wgrad_reduce(c.row.slabs, ws, dy->c, x->c, perm_r, dy_scale, accumulate, dw, dbias, s);
+    default: {
+      if (c.gen.ntiles == 0) return VSRK_OK;
+      const int st = wgrad_generic(d, x, dy, pro_scale, pro_shift, perm_r, dbias != nullptr, ws, c.gen, s);
+      return st != VSRK_OK ? st : wgrad_reduce(c.gen.slabs, ws, dy->c, x->c, perm_r, dy_scale, accumulate, dw, dbias, s);
+    }
+  }
 }

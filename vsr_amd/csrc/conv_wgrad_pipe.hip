@@ -22,23 +22,15 @@
 //  * the prologue's per-channel scale/shift live in registers (every thread
 //    stages one fixed 8-channel chunk position), the ReLU is compile-time and
 //    16-bit packing is v_cvt_pk_{bf16,f16}_f32 on vector converts.
-#include "conv_common.h"
-
+#include "conv_wgrad.h"
 
 namespace {
 using namespace vsrk_conv;
 
-typedef __amdgpu_buffer_rsrc_t Rsrc;
-constexpr uint32_t OOB = 0x80000000u;
-__device__ __forceinline__ Rsrc rsrc_at(const void* base) {
-  const uint64_t b = (uint64_t)base;
-  const uint64_t u = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32)) << 32) |
-                     (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
-  return __builtin_amdgcn_make_buffer_rsrc((void*)u, 0, 0x7FFFFFF0, 0x00020000);
-}
-__device__ __forceinline__ uint4 bload16(Rsrc r, uint32_t off) {
-  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0));
-}
+using rawbuf::bload16;
+using rawbuf::OOB;
+using rawbuf::rsrc_at;
+using rawbuf::Rsrc;
 
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));

@@ -24,11 +24,11 @@
 //    the halo row and column separately and every fragment address is a
 //    per-lane base plus a compile-time offset.  Transposed reads are
 //    conflict-free.
-//  * Deterministic: per-(split, row half) fp32 slabs in conv_wgrad.hip's
-//    layout ([9 taps][32 co][32 ci] + dbias per kd "combo"), summed in a
-//    fixed order by wgrad_reduce_kernel.  dbias: an MFMA against ones on each
+//  * Deterministic: per-(split, row half) fp32 slabs ([9 taps][32 co][32 ci]
+//    + dbias per kd "combo": the WgradSlabs of vsrk_wgrad_roll_plan), summed
+//    in a fixed order by wgrad_reduce.  dbias: an MFMA against ones on each
 //    dy slice once (workgroups of input chunk 0).
-#include "conv_common.h"
+#include "conv_wgrad.h"
 
 namespace {
 using namespace vsrk_conv;
@@ -98,16 +98,6 @@ __device__ __forceinline__ void wr_wait_vmcnt() {
   __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
 }
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-template <typename H> struct V8W;
-template <> struct V8W<bf16> { typedef bf16x8 type; };
-template <> struct V8W<f16> { typedef f16x8 type; };
-__device__ __forceinline__ f32x4_t mfma16(bf16x8 a, bf16x8 b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4_t mfma16(f16x8 a, f16x8 b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
 // 8 consecutive voxels (k) of one channel: two transposed 4-row reads
 __device__ __forceinline__ uint4 tr_frag(const char* p0, const char* p1) {
   const v4i16 a = ds_read_tr(p0);
@@ -121,7 +111,7 @@ struct WTile {
 
 template <int PRO, typename H>
 __global__ __launch_bounds__(WNW * 64, 2) void wgrad_roll_kernel(WRArgs a) {
-  using V8 = typename V8W<H>::type;
+  using V8h = typename V8<H>::type;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -355,7 +345,7 @@ __global__ __launch_bounds__(WNW * 64, 2) void wgrad_roll_kernel(WRArgs a) {
             const uint4* xf = xw[(r + kh) % 3];
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw)
-              acc[kd][kh][kw] = mfma16(__builtin_bit_cast(V8, yf[kd]), __builtin_bit_cast(V8, xf[kw]), acc[kd][kh][kw]);
+              acc[kd][kh][kw] = mfma16x32(__builtin_bit_cast(V8h, yf[kd]), __builtin_bit_cast(V8h, xf[kw]), acc[kd][kh][kw]);
           }
         }
       }
@@ -369,13 +359,13 @@ __global__ __launch_bounds__(WNW * 64, 2) void wgrad_roll_kernel(WRArgs a) {
           if ((km >> kd) & 1) {
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw)
-              acc[kd][kh][kw] = mfma16(__builtin_bit_cast(V8, yf[kd]), __builtin_bit_cast(V8, xf[kw]), acc[kd][kh][kw]);
+              acc[kd][kh][kw] = mfma16x32(__builtin_bit_cast(V8h, yf[kd]), __builtin_bit_cast(V8h, xf[kw]), acc[kd][kh][kw]);
           }
         }
       }
 #endif
       if (do_bias && cih == 0 && newy)
-        bacc = mfma16(__builtin_bit_cast(V8, yf[0]), __builtin_bit_cast(V8, ones), bacc);
+        bacc = mfma16x32(__builtin_bit_cast(V8h, yf[0]), __builtin_bit_cast(V8h, ones), bacc);
     }
   };
 
@@ -513,10 +503,8 @@ namespace {
 }  // namespace
 
 // The plan of the rolling weight gradient for a request, or false when the
-// request is not eligible.  Workspace: nsplit*2 x (3 * nci * nco) slabs of
-// (9 * 1024 + 32) floats.
-bool vsrk_wgrad_roll_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy, int* nsplit,
-                          int* tps, int* ntiles, int* dzc, size_t* ws_bytes) {
+// request is not eligible.
+bool vsrk_wgrad_roll_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy, VsrkRollPlan* p) {
   const int mode = vsrk_path_mode(VSRK_PATH_WGRAD_ROLL);  // 0 off, 1 forced on, 2 automatic
   if (mode == 0) return false;
   // automatic mode: with a single output depth the kd-tap reuse of the
@@ -559,23 +547,30 @@ bool vsrk_wgrad_roll_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, const 
   if (vsrk_g_grid_cap > 0) splits = std::max(1, std::min(splits, vsrk_g_grid_cap));
   const int t = (int)ceil_div64(nt, splits);
   splits = (int)ceil_div64(nt, t);
-  *nsplit = splits;
-  *tps = t;
-  *ntiles = (int)nt;
-  *dzc = z;
-  *ws_bytes = (size_t)2 * splits * 3 * combos * (9 * 1024 + 32) * sizeof(float);
+  p->nsplit = splits;
+  p->tps = t;
+  p->ntiles = (int)nt;
+  p->dzc = z;
+  // the kernel's slabs (its last block): a workgroup's two row halves write
+  // slabs 2 * split and 2 * split + 1 of each kd's combo, 32 x 32 channels
+  // and 9 taps each; the dbias sums ride on kd = min(pd, 2), the tap whose dy
+  // slices are all of dy
+  WgradSlabs& sl = p->slabs;
+  sl.nsplit = 2 * splits;
+  sl.slab = 9 * 1024 + 32;
+  sl.kd = sl.kh = sl.kw = 3;
+  sl.nco_t = nco; sl.nci_t = nci;
+  sl.cot_w = sl.cit_w = 32;
+  sl.kd_bias = std::min(d->pd, 2);
+  sl.rows_ok = true;
   return true;
 }
 
-// 1 = launched the slab kernel (the caller reduces with nsplit * 2 splits,
-// 3 * nci * nco combos of 32 x 32 channels, slab 9 * 1024 + 32); 0 = not eligible.
-int vsrk_conv_wgrad_roll(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy,
-                         const float* pro_scale, const float* pro_shift, int want_bias, float* ws, size_t ws_bytes,
-                         int* nsplit_out, hipStream_t s) {
-  int nsplit, tps, ntiles, dzc;
-  size_t need;
-  if (!vsrk_wgrad_roll_plan(d, x, dy, &nsplit, &tps, &ntiles, &dzc, &need)) return 0;
-  if (ws_bytes < need) return 0;
+// Launches the plan's slab kernel.
+void vsrk_conv_wgrad_roll(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy,
+                          const float* pro_scale, const float* pro_shift, int want_bias, float* ws,
+                          const VsrkRollPlan& p, hipStream_t s) {
+  const int nsplit = p.nsplit, tps = p.tps, ntiles = p.ntiles, dzc = p.dzc;
   const int pro = d->prologue & (VSRK_PRO_AFFINE | VSRK_PRO_RELU);
   WRArgs a;
   a.x = (const char*)x->ptr;
@@ -598,8 +593,8 @@ int vsrk_conv_wgrad_roll(const vsrk_conv_desc* d, const vsrk_tensor5* x, const v
   a.nsplit = nsplit;
   a.nci_chunks = x->c / 32;
   a.nco_tiles = dy->c / 32;
-  a.slab = 9 * 1024 + 32;
-  a.kd_bias = std::min(d->pd, 2);
+  a.slab = p.slabs.slab;
+  a.kd_bias = p.slabs.kd_bias;
   a.prio = vsrk_g_roll_prio;
   a.tiles_w = make_rdivw(ceil_div(dy->w, TW));
   a.tiles_h = make_rdivw(ceil_div(dy->h, WTH));
@@ -613,6 +608,4 @@ int vsrk_conv_wgrad_roll(const vsrk_conv_desc* d, const vsrk_tensor5* x, const v
     kern<<<grid, WNW * 64, lds, s>>>(a);
     return 0;
   });
-  *nsplit_out = nsplit;
-  return 1;
 }

@@ -30,13 +30,13 @@
 //    of voxel j sits at chunk c ^ (2 bit1(j) + 4 bit3(j)).  Every transposed
 //    read is conflict-free whatever its voxel offset (the kw taps shift it by
 //    0..2), and so is every 16-byte store (8 lanes fill one voxel's 128 B).
-//  * Deterministic: one fp32 slab per (band, channel chunk) in
-//    wgrad_reduce_kernel's layout ([9 taps][64 co][64 ci] + dbias), summed
-//    over bands in a fixed order.  dbias: MFMAs of the dy fragments against
+//  * Deterministic: one fp32 slab per (band, channel chunk) ([9 taps][64 co]
+//    [64 ci] + dbias: the WgradSlabs of vsrk_wgrad_row_plan), summed over
+//    bands in a fixed order by wgrad_reduce.  dbias: MFMAs of the dy fragments against
 //    ones, wave (half, quarter q) on k-chunk q (two per wave and stage), the
 //    four k-chunks' partials added through LDS at the end.
 #include <algorithm>
-#include "conv_common.h"
+#include "conv_wgrad.h"
 
 namespace {
 using namespace vsrk_conv;
@@ -64,28 +64,13 @@ constexpr uint32_t RW_OOB = 0x80000000u;               // buffer offset past the
 
 __host__ __device__ constexpr int rw_swz(int j) { return 2 * ((j >> 1) & 1) + 4 * ((j >> 3) & 1); }
 
-typedef __amdgpu_buffer_rsrc_t RwRsrc;
-__device__ __forceinline__ RwRsrc rw_rsrc(const void* base) {
-  const uint64_t b = (uint64_t)base;
-  const uint64_t u = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32)) << 32) |
-                     (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
-  return __builtin_amdgcn_make_buffer_rsrc((void*)u, 0, 0x7FFFFFF0, 0x00020000);
-}
+using rawbuf::rsrc_at;
+typedef rawbuf::Rsrc RwRsrc;
 typedef uint32_t rw_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void rw_st16(uint32_t addr, uint4 v) {
   *(__attribute__((address_space(3))) rw_u32x4*)(size_t)addr = __builtin_bit_cast(rw_u32x4, v);
 }
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-template <typename H> struct V8R;
-template <> struct V8R<bf16> { typedef bf16x8 type; };
-template <> struct V8R<f16> { typedef f16x8 type; };
-__device__ __forceinline__ f32x4_t rw_mfma(bf16x8 a, bf16x8 b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4_t rw_mfma(f16x8 a, f16x8 b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
 // 8 consecutive voxels (k) of one channel: two transposed 4-row reads (LDS
 // byte addresses: no generic-pointer arithmetic or null checks)
 __device__ __forceinline__ uint4 rw_frag(uint32_t p0, uint32_t p1) {
@@ -122,7 +107,7 @@ struct RowArgs {
 
 template <typename H, bool SPM>
 __global__ __launch_bounds__(RW_NW * 64, 1) void wgrad_row_kernel(RowArgs a) {
-  using V8 = typename V8R<H>::type;
+  using V8h = typename V8<H>::type;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -178,8 +163,8 @@ __global__ __launch_bounds__(RW_NW * 64, 1) void wgrad_row_kernel(RowArgs a) {
     const bool xok = xr >= 0 && xr < a.H;
     const int yr = t - 2;
     const bool yok = yr >= 0 && yr < nst;
-    const RwRsrc rx = rw_rsrc(xim + 2 * (int64_t)(xok ? xr : 0) * a.xsh);
-    const RwRsrc ry = rw_rsrc(yim + 2 * (int64_t)(h0 + (yok ? yr : 0)) * a.ysh);
+    const RwRsrc rx = rsrc_at(xim + 2 * (int64_t)(xok ? xr : 0) * a.xsh);
+    const RwRsrc ry = rsrc_at(yim + 2 * (int64_t)(h0 + (yok ? yr : 0)) * a.ysh);
 #pragma unroll
     for (int q = 0; q < RW_NQ; ++q) {
       const bool isx = q != 2 && q != 3;
@@ -304,13 +289,13 @@ __global__ __launch_bounds__(RW_NW * 64, 1) void wgrad_row_kernel(RowArgs a) {
 #pragma unroll
         for (int b = 0; b < 2; ++b)
           if (RW_ABL & 2) acc[kh][kw][b][0] += __builtin_bit_cast(float, yf[kc & 1][b].x ^ xf[G & 1][kw].y);
-          else acc[kh][kw][b] = rw_mfma(__builtin_bit_cast(V8, yf[kc & 1][b]), __builtin_bit_cast(V8, xf[G & 1][kw]),
+          else acc[kh][kw][b] = mfma16x32(__builtin_bit_cast(V8h, yf[kc & 1][b]), __builtin_bit_cast(V8h, xf[G & 1][kw]),
                                    acc[kh][kw][b]);
       }
       if (kh == 1 && kc == cib) {  // wave-uniform
 #pragma unroll
         for (int b = 0; b < 2; ++b)
-          bacc[b] = rw_mfma(__builtin_bit_cast(V8, yf[kc & 1][b]), __builtin_bit_cast(V8, ones), bacc[b]);
+          bacc[b] = mfma16x32(__builtin_bit_cast(V8h, yf[kc & 1][b]), __builtin_bit_cast(V8h, ones), bacc[b]);
       }
       if (a.prio) __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
@@ -410,18 +395,23 @@ bool vsrk_wgrad_row_plan(const vsrk_conv_desc* d, const vsrk_tensor5* x, const v
   p->ncic = ncic;
   const int64_t ns = images * p->bands * nseg;
   if (ns * ncot * ncic >= (1ll << 30)) return false;
-  p->nsplit = (int)ns;
-  p->cot_w = RW_COW;
-  p->slab = RW_SLAB;
-  p->ws_bytes = (size_t)ns * ncot * ncic * RW_SLAB * sizeof(float);
+  // the kernel's slabs (its last block): one per (image, band, segment) and
+  // block of RW_COW x 64 channels.  The per-output reduce only: the row-order
+  // one sums the same slabs in another order.
+  WgradSlabs& sl = p->slabs;
+  sl.nsplit = (int)ns;
+  sl.slab = RW_SLAB;
+  sl.kd = 1; sl.kh = sl.kw = 3;
+  sl.nco_t = ncot; sl.nci_t = ncic;
+  sl.cot_w = RW_COW; sl.cit_w = 64;
+  sl.kd_bias = 0;
+  sl.rows_ok = false;
   return true;
 }
 
-int vsrk_conv_wgrad_row(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy, int want_bias,
-                        float* ws, size_t ws_bytes, VsrkRowPlan* plan, hipStream_t s) {
-  VsrkRowPlan p;
-  if (!vsrk_wgrad_row_plan(d, x, dy, &p)) return 0;
-  if (ws_bytes < p.ws_bytes) return 0;
+// Launches the plan's slab kernel.
+void vsrk_conv_wgrad_row(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy, int want_bias,
+                         float* ws, const VsrkRowPlan& p, hipStream_t s) {
   RowArgs a;
   a.x = (const char*)x->ptr;
   a.dy = (const char*)dy->ptr;
@@ -457,10 +447,10 @@ int vsrk_conv_wgrad_row(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vs
   a.nseg = p.nseg;
   a.ncot = p.ncot;
   a.ncic = p.ncic;
-  a.nsplit = p.nsplit;
+  a.nsplit = p.slabs.nsplit;
   a.want_bias = want_bias;
   a.prio = g_wrow_prio;
-  const int grid = p.nsplit * p.ncot * p.ncic;
+  const int grid = p.slabs.nsplit * p.ncot * p.ncic;
   vsrk_dispatch16(x->dtype, [&](auto tag) {
     using H = decltype(tag);
     auto kern = spm ? wgrad_row_kernel<H, true> : wgrad_row_kernel<H, false>;
@@ -468,6 +458,4 @@ int vsrk_conv_wgrad_row(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vs
     kern<<<grid, RW_NW * 64, RW_LDS, s>>>(a);
     return 0;
   });
-  *plan = p;
-  return 1;
 }

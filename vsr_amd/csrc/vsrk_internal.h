@@ -75,8 +75,8 @@ int vsrk_conv_fwd_roll_fold(const vsrk_conv_desc* d, const vsrk_tensor5* x, cons
 int vsrk_conv_fwd_row(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed, const float* bias,
                       const vsrk_tensor5* residual, const vsrk_tensor5* mask, const vsrk_tensor5* y, hipStream_t s);
 
-// pointwise (1x1x1) bf16 conv (conv_pw.hip): forward / data gradient and
-// weight gradient; same return convention (the wgrad launches its own reduce)
+// pointwise (1x1x1) bf16 conv (conv_pw.hip): forward / data gradient; same
+// return convention (its weight gradient: conv_wgrad.h)
 int vsrk_conv_fwd_pw(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed, const float* bias,
                      const float* pro_scale, const float* pro_shift, const vsrk_tensor5* residual,
                      const vsrk_tensor5* mask, const vsrk_tensor5* y, hipStream_t s);
@@ -88,10 +88,6 @@ int vsrk_conv_fwd_pw_pbwd(const vsrk_conv_desc* d, const vsrk_tensor5* x, const 
                           const vsrk_tensor5* mask, const vsrk_tensor5* y, int c_lo, const vsrk_slope_out* slope,
                           hipStream_t s);
 size_t vsrk_pw_pbwd_ws_bytes();
-size_t vsrk_conv_wgrad_pw_workspace(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy);
-int vsrk_conv_wgrad_pw(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vsrk_tensor5* dy,
-                       const float* pro_scale, const float* pro_shift, float dy_scale, int32_t perm_r, float* dw,
-                       float* dbias, int32_t accumulate, void* workspace, size_t workspace_bytes, hipStream_t s);
 
 // ---- dispatch state (conv_paths.hip) ----
 // One mode per kernel family, resolved from the family's environment variable
