@@ -201,6 +201,16 @@ int vsrk_conv_set_algo(int32_t mode);
 int vsrk_conv_set_path(const char* path, int32_t mode);
 int vsrk_conv_get_path(const char* path, int32_t* mode);
 
+/* The switch of the row-walking 3x3 64 -> 256 conv through a shuffle-2 output
+ * view (EDSR's up-sampler forward, reached through path "roll"): a knob of
+ * its own beside the table above, with the table's rules.  Read once from
+ * VSRK_CONV_ROW_WIDE at load (unset = -1: the shapes that measured faster than
+ * the tile kernel; '0...' = 0: off; any other value = 1: every eligible
+ * shape); set: 0, 1, or -1 = back to the value at load.  A process-wide test /
+ * A-B switch like the paths. */
+int vsrk_conv_set_row_wide(int32_t mode);
+int vsrk_conv_get_row_wide(int32_t* mode);
+
 /* Test knob: cap the persistent conv grids (forward / data-gradient kernels)
  * and the weight-gradient split at max_workgroups (0 = default: one
  * workgroup per CU and the split rule).  With a small cap a small shape runs

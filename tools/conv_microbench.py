@@ -1,6 +1,10 @@
 """Standalone timing of the conv kernels at the cfg-2 shapes (for rocprofv3
---pmc passes and A/B work).  Prints one line per case: mean ms and TFLOP/s."""
+--pmc passes and A/B work).  Prints one line per case: mean ms and TFLOP/s.
+With --ab PATH=M0/M1 the two modes of a path alternate in one process for
+--rounds rounds of --iters launches each and the line gives each arm's median
+round (and its min .. max)."""
 import argparse
+import statistics
 import sys
 from pathlib import Path
 
@@ -33,6 +37,10 @@ CASES = {
     # EDSR tail conv F -> 1 at HR (thin-channel kernels: fwd = thin-out, dgrad = thin-in)
     "tail": (64, 1, 512, 512, 64, 1, (1, 3, 3), (0, 1, 1)),
     "head": (64, 1, 128, 128, 1, 64, (1, 3, 3), (0, 1, 1)),
+    # EDSR's up-sampler convs 64 -> 256 written through a shuffle-2 view (a 9th
+    # field: y_shuffle; forward only): tail.0.conv1 and tail.0.conv2 of the x4 net
+    "up1": (64, 1, 128, 128, 64, 256, (1, 3, 3), (0, 1, 1), 2),
+    "up2": (64, 1, 256, 256, 64, 256, (1, 3, 3), (0, 1, 1), 2),
 }
 
 
@@ -52,6 +60,8 @@ def main():
     ap.add_argument("--what", default="fwd,res,wgrad")
     ap.add_argument("--yf32", action="store_true", help="fp32 forward output (DUF's filter head)")
     ap.add_argument("--paths", default="", help="e.g. k3=0,fast=1 (vsrk_conv_set_path)")
+    ap.add_argument("--ab", default="", help="e.g. row_wide=0/1: alternate two modes of a path, medians over --rounds")
+    ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--stamps", action="store_true",
                     help="after each case, print the s_memtime stamps of a ROLL_STAMP diagnostic build")
     args = ap.parse_args()
@@ -60,14 +70,21 @@ def main():
         p, m = kv.split("=")
         F.set_conv_path(p, int(m))
     dev = "cuda"
-    n, d, h, w, ci, co, k, pad = CASES[args.case]
+    n, d, h, w, ci, co, k, pad, *rest = CASES[args.case]
+    ysh = rest[0] if rest else 1
     dt = torch.bfloat16
     g = torch.Generator(device="cpu").manual_seed(0)
     x = _padded(torch.randn((n, d, h, w, ci), generator=g), dt)
     wt = (torch.randn((co, ci, *k), generator=g) * 0.05).to(dev)
     b = torch.randn(co, generator=g).to(dev)
     do = d + 2 * pad[0] - k[0] + 1
-    y = torch.empty((n, do, h, w, co), dtype=dt if co >= 8 and not args.yf32 else torch.float32, device=dev)
+    y = torch.empty((n, do, h * ysh, w * ysh, co // (ysh * ysh)),
+                    dtype=dt if co >= 8 and not args.yf32 else torch.float32, device=dev)
+    flop = 2.0 * n * do * h * w * co * ci * k[0] * k[1] * k[2]
+    if ysh > 1:  # a sub-pixel output view: the forward alone
+        wps = F.pack_weight(wt, 0, dt, perm_r=ysh)
+        return run_cases(args, {"fwd": lambda: F.conv(x, wps, y, k, pad, bias=b, y_shuffle=ysh)}, flop,
+                         {"fwd": x.numel() * 2 + y.numel() * 2})
     res = torch.randn((n, do, h, w, co), generator=g).to(dev, y.dtype)
     gy = _padded(torch.randn((n, do, h, w, co), generator=g), dt)
     dx = torch.empty((n, d, h, w, ci), dtype=dt if ci >= 8 else torch.float32, device=dev)
@@ -86,7 +103,6 @@ def main():
     wp = F.pack_weight(wt, 0, dt)
     psc = torch.rand(ci, generator=g).to(dev) + 0.5
     psh = torch.randn(ci, generator=g).to(dev)
-    flop = 2.0 * n * do * h * w * co * ci * k[0] * k[1] * k[2]
     cases = {
         "fwd": lambda: F.conv(x, wp, y, k, pad, bias=b),
         "fwdpro": lambda: F.conv(x, wp, y, k, pad, bias=b, prologue=F.PRO_AFFINE_RELU, pro_scale=psc, pro_shift=psh),
@@ -104,18 +120,46 @@ def main():
     bnx = torch.randn((n, d, h, w, ci), generator=g).to(dev, dt) if ci >= 8 else None
     st = torch.stack([torch.rand(ci, generator=g) + 0.5, torch.randn(ci, generator=g) * 0.1,
                       torch.randn(ci, generator=g) * 0.1, torch.rand(ci, generator=g) + 0.5]).to(dev)
+    run_cases(args, cases, flop, nbytes)
+
+
+def _time(fn, iters):
+    """mean ms of `iters` launches between two events"""
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(iters):
+        fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / iters
+
+
+def run_cases(args, cases, flop, nbytes):
     for name in args.what.split(","):
         fn = cases[name]
         for _ in range(3):
             fn()
         torch.cuda.synchronize()
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        for _ in range(args.iters):
-            fn()
-        e.record()
-        torch.cuda.synchronize()
-        ms = s.elapsed_time(e) / args.iters
+        if args.ab:
+            path, modes = args.ab.split("=")
+            arms = [int(m) for m in modes.split("/")]
+            t = {m: [] for m in arms}
+            for m in arms:  # each arm's first launch (kernel load) outside the rounds
+                F.set_conv_path(path, m)
+                fn()
+            for _ in range(args.rounds):
+                for m in arms:
+                    F.set_conv_path(path, m)
+                    t[m].append(_time(fn, args.iters))
+            F.set_conv_path(path, -1)
+            for m in arms:
+                ms = statistics.median(t[m])
+                print(f"{args.case:10s} {name:6s} {path}={m}: median {ms * 1e3:9.1f} us  "
+                      f"(min {min(t[m]) * 1e3:.1f} .. max {max(t[m]) * 1e3:.1f}, {args.rounds} rounds x {args.iters})  "
+                      f"{flop / ms / 1e9:8.1f} TFLOP/s  {nbytes.get(name, 0) / ms / 1e9:7.2f} TB/s (min HBM bytes)",
+                      flush=True)
+            continue
+        ms = _time(fn, args.iters)
         print(f"{args.case:10s} {name:6s} {ms * 1e3:9.1f} us  {flop / ms / 1e9:8.1f} TFLOP/s  "
               f"({flop / ms / 1e9 / 2500 * 100:.1f}% of 2.5 PF)  "
               f"{nbytes.get(name, 0) / ms / 1e9:7.2f} TB/s (min HBM bytes)", flush=True)

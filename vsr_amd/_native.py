@@ -126,6 +126,8 @@ _SIGS = {
     "vsrk_conv_set_algo": (C.c_int, [C.c_int32]),
     "vsrk_conv_set_path": (C.c_int, [C.c_char_p, C.c_int32]),
     "vsrk_conv_get_path": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32)]),
+    "vsrk_conv_set_row_wide": (C.c_int, [C.c_int32]),
+    "vsrk_conv_get_row_wide": (C.c_int, [C.POINTER(C.c_int32)]),
     "vsrk_conv_set_grid_cap": (C.c_int, [C.c_int32]),
     "vsrk_conv_set_roll_depth": (C.c_int, [C.c_int32]),
     "vsrk_subpixel_conv_weight": (C.c_int, [_P, _P] + [C.c_int32] * 6 + [_P, _P, _P]),

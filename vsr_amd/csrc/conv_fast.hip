@@ -21,9 +21,9 @@ int vsrk_conv_fwd_fast(const vsrk_conv_desc* d, const vsrk_tensor5* x, const voi
                        const vsrk_tensor5* mask, const vsrk_tensor5* y, hipStream_t s) {
   if (vsrk_path_mode(VSRK_PATH_FAST) == 0) return 0;
   if (!vsrk_is16(x->dtype)) return 0;
-  // (2: launched on the rolling family, for the dispatch log)
+  // (2: launched on the rolling family, 3: on its wide row kernel, for the dispatch log)
   if (const int rl = vsrk_conv_fwd_roll(d, x, w_packed, bias, pro_scale, pro_shift, residual, mask, y, s))
-    return rl > 0 ? 2 : rl;
+    return rl > 0 ? 1 + rl : rl;
   if (d->act < VSRK_ACT_NONE || d->act > VSRK_ACT_PRELU) return 0;  // (PReLU of the sum: rolling or tile kernel)
   if (!chunk_ok(x, 2) || x->c % 8 != 0) return 0;
   const int xr = x->shuffle > 1 ? x->shuffle : 1, yr = y->shuffle > 1 ? y->shuffle : 1;

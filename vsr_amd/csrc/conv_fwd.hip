@@ -557,7 +557,7 @@ extern "C" int vsrk_conv_fwd(const vsrk_conv_desc* d, const vsrk_tensor5* x, con
   }
   const int fast = vsrk_conv_fwd_fast(d, x, w_packed, bias, pro_scale, pro_shift, residual, mask, y, s);
   if (fast != 0) {
-    logd(fast == 2 ? "roll" : "fast");
+    logd(fast == 3 ? "row_wide" : fast == 2 ? "roll" : "fast");
     return fast > 0 ? VSRK_OK : -fast;
   }
   logd("tile");

@@ -30,6 +30,11 @@ int vsrk_num_cus() {
 }
 
 int vsrk_g_path_mode[VSRK_PATH_COUNT];  // filled below, at load
+// The wide row conv's switch (conv_row_wide.hip) is a knob of its own, read
+// from VSRK_CONV_ROW_WIDE by the table's rule: the table of named paths is
+// pinned by tests/test_paths_cpu.py.  -1: the shapes that measured faster
+// than the tile kernel, 0 off, 1 every eligible shape.
+int vsrk_g_row_wide_mode;
 
 namespace {
 
@@ -57,10 +62,12 @@ constexpr PathInfo kPaths[VSRK_PATH_COUNT] = {
 };
 
 int g_load_mode[VSRK_PATH_COUNT];  // the modes resolved at load (what mode -1 restores)
+int g_row_wide_load;               // ... and of vsrk_conv_set_row_wide
 
 const bool g_paths_loaded = [] {
   for (int i = 0; i < VSRK_PATH_COUNT; ++i)
     vsrk_g_path_mode[i] = g_load_mode[i] = vsrk_env_flag(kPaths[i].env, kPaths[i].unset);
+  vsrk_g_row_wide_mode = g_row_wide_load = vsrk_env_flag("VSRK_CONV_ROW_WIDE", -1);
   return true;
 }();
 
@@ -94,6 +101,18 @@ extern "C" int vsrk_conv_get_path(const char* path, int32_t* mode) {
   const int i = find_path(path);
   if (i < 0) return VSRK_ERR_INVALID;
   *mode = vsrk_g_path_mode[i];
+  return VSRK_OK;
+}
+
+extern "C" int vsrk_conv_set_row_wide(int32_t mode) {
+  VSRK_CHECK(mode >= -1 && mode <= 1, "conv_set_row_wide: mode %d outside [-1, 1]", mode);
+  vsrk_g_row_wide_mode = mode < 0 ? g_row_wide_load : mode;
+  return VSRK_OK;
+}
+
+extern "C" int vsrk_conv_get_row_wide(int32_t* mode) {
+  VSRK_CHECK(mode, "conv_get_row_wide: null argument");
+  *mode = vsrk_g_row_wide_mode;
   return VSRK_OK;
 }
 

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void roll_bnred_final_kernel(const float* __re
 
 size_t vsrk_roll_slope_ws_bytes() { return (size_t)vsrk_num_cus() * RNW * sizeof(double); }
 
-// 1 = launched, 0 = not eligible, < 0 = -(error status)
+// 1 = launched (2: on the wide row kernel), 0 = not eligible, < 0 = -(error status)
 static int roll_fwd_one(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed, const float* bias,
                         const float* pro_scale, const float* pro_shift, const vsrk_tensor5* residual,
                         const vsrk_tensor5* mask, const vsrk_tensor5* y, hipStream_t s, const vsrk_slope_out* slope,
@@ -201,6 +201,12 @@ static int roll_fwd_one(const vsrk_conv_desc* d, const vsrk_tensor5* x, const vo
   // of the tile kernel's two forms: the row kernel stands aside.
   if (!k3 && sp == SP_NONE && !pmask && !bnred && wres_mode == 1) {
     if (const int rw = vsrk_conv_fwd_row(d, x, w_packed, bias, residual, mask, y, s)) return rw;
+  }
+  // EDSR's 64 -> 256 up-sampler convs through a shuffle-2 output view: the
+  // wide row-walking kernel (conv_row_wide.hip); 2 = launched there (the
+  // dispatch log tells it from the tile kernel)
+  if (sp == SP_Y && !k3 && !pmask && !bnred) {
+    if (const int rw = vsrk_conv_fwd_row_wide(d, x, w_packed, bias, residual, mask, y, s)) return rw > 0 ? 2 : rw;
   }
   // a shuffled view walks the low-res grid: its row / column strides are r
   // physical rows / columns (the phase lives in the channel offset table)

@@ -64,47 +64,16 @@
 //    conv_roll's epilogue_sw): every global access is 16 contiguous bytes.
 //    The operand rows (residual, mask, old output for accumulate) are loaded
 //    into registers one stage ahead.  Rounds once, at the store.
-#include "conv_common.h"
+#include "conv_row_common.h"
 
 namespace {
 using namespace vsrk_conv;
 
-constexpr int CR_NW = 8;                       // waves
-constexpr int CR_SEG = 128;                    // output columns per segment
-constexpr int CR_SLOT = (CR_SEG + 2) * 128;    // 16,640 B: columns -1 .. 128 of one input row
-constexpr int CR_NSLOT = 4;
 constexpr int CR_BIAS = CR_NSLOT * CR_SLOT;    // [64] bias * out_scale
 constexpr int CR_LDS = CR_BIAS + 256;          // 66,816 B
-constexpr int CR_MINBAND = 4;                  // rows: a band pays 2 halo rows and the weight load
-constexpr uint32_t CR_OOB = 0x80000000u;       // buffer offset past the range: loads read zero, stores are dropped
 enum { CE_RES = 1, CE_MASK = 2, CE_ACC = 4, CE_RELU = 8 };
 
-typedef rawbuf::Rsrc CrRsrc;
-typedef int cr_v4i __attribute__((ext_vector_type(4)));
 using rawbuf::rsrc_at;
-// byte offset = voff (per lane; CR_OOB: out of range) + soff (wave-uniform,
-// < 2^31: the row and the q-th voxel group, so a lane keeps one offset per view)
-__device__ __forceinline__ uint4 cr_load16(CrRsrc r, uint32_t voff, uint32_t soff) {
-  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
-}
-// A store keeps its whole offset in the VGPR: with a register in the scalar
-// offset field the compiler assumes that a 16-byte store has read its data by
-// the time the next VALU instruction overwrites the data registers, and pads
-// nothing -- on gfx950 the store can still be reading them (seen in some
-// launches only: one dword of the 16 bytes, in the last four lanes of each
-// 16-lane row, took the next voxel group's value).  Without a scalar offset
-// the compiler inserts the wait states of that hazard itself.
-__device__ __forceinline__ void cr_store16(CrRsrc r, uint32_t voff, uint4 v) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(cr_v4i, v), r, (int)voff, 0, 0);
-}
-
-// a view of (images, H, W, 64 channels): element strides (the host checks
-// that every byte offset inside one image fits the buffer range)
-struct CrView {
-  const char* ptr;
-  int64_t sn, sd;
-  int sh, sw;
-};
 
 struct ConvRowArgs {
   CrView x, y, res, msk;
@@ -154,9 +123,9 @@ __global__ __launch_bounds__(CR_NW * 64, 1) void conv_row_kernel(ConvRowArgs a) 
   uint32_t fa[3], fh[3];
 #pragma unroll
   for (int kw = 0; kw < 3; ++kw) {
-    const int lv = vq * 32 + r + kw, sz = (lv >> 1) & 7;
-    fa[kw] = (uint32_t)(lv * 128 + ((hf ^ (sz & 1)) << 4));
-    fh[kw] = (uint32_t)(sz >> 1);
+    const int lv = vq * 32 + r + kw;
+    fa[kw] = cr_frag_base(lv, hf);
+    fh[kw] = cr_frag_swz(lv);
   }
   // staging roles: q = 0, 1: column 8 wave + lane / 8 + 64 q of the segment,
   // piece lane & 7 (64 voxels apart: the same swizzle, 8 KB apart in the
@@ -165,8 +134,8 @@ __global__ __launch_bounds__(CR_NW * 64, 1) void conv_row_kernel(ConvRowArgs a) 
   constexpr int NSQ = HALO ? 3 : 2;
   const int scol = 8 * wave + (lane >> 3);
   const int hcol = (lane >> 3) == 0 ? -1 : CR_SEG;
-  const uint32_t sdst = (uint32_t)((scol + 1) * 128 + ((sp ^ (((scol + 1) >> 1) & 7)) << 4));
-  const uint32_t hdst = (uint32_t)((hcol + 1) * 128 + ((sp ^ (((hcol + 1) >> 1) & 7)) << 4));
+  const uint32_t sdst = CR_STAGE_DST(scol, sp);
+  const uint32_t hdst = CR_STAGE_DST(hcol, sp);
   const bool halo_lane = wave == 0 && lane < 16;
 
   f32x16 b0, b1;
@@ -205,20 +174,9 @@ __global__ __launch_bounds__(CR_NW * 64, 1) void conv_row_kernel(ConvRowArgs a) 
     // written to LDS at the end of the NEXT stage, so two rows are in flight
     // and at most two sets are live)
     uint4 stq[CR_NSLOT][NSQ];
-    auto load_row = [&](int row, uint4 (&st)[NSQ]) __attribute__((always_inline)) {
-      const bool rv = row >= 0 && row < a.H && row <= r1;
-      const uint32_t rb = rv ? 2u * (uint32_t)(row * a.x.sh) : 0u;
-#pragma unroll
-      for (int q = 0; q < 2; ++q) st[q] = cr_load16(rx, (rv && xok[q]) ? xcolb : CR_OOB, rb + 2u * (uint32_t)(64 * q * a.x.sw));
-      if constexpr (HALO) st[2] = cr_load16(rx, (rv && xok[2]) ? hcolb : CR_OOB, rb);
-    };
+    const CrLoadRow<HALO, ConvRowArgs> load_row{a, r1, xok, xcolb, rx, hcolb};
     auto write_row = [&](int slot, const uint4 (&st)[NSQ]) __attribute__((always_inline)) {
-      char* sl = lds + slot * CR_SLOT;
-#pragma unroll
-      for (int q = 0; q < 2; ++q) *reinterpret_cast<uint4*>(sl + sdst + q * 64 * 128) = st[q];
-      if constexpr (HALO) {
-        if (halo_lane) *reinterpret_cast<uint4*>(sl + hdst) = st[NSQ - 1];
-      }
+      cr_write_row<HALO>(lds + slot * CR_SLOT, st, sdst, hdst, halo_lane);
     };
 
     // epilogue operands of output row `orow`, one stage ahead of its flush
@@ -236,32 +194,12 @@ __global__ __launch_bounds__(CR_NW * 64, 1) void conv_row_kernel(ConvRowArgs a) 
     };
 
     // Flush of a finished bank = output row `orow` (a row outside the band
-    // takes out-of-range offsets: nothing is stored).  Lane (r, hf) holds
-    // voxel r, channels 8 g + 4 hf + i in register 4 g + i; the swaps leave it
-    // chunk ecc of voxels (r & 15) + 16 q in registers 8 q .. + 7 (see
-    // conv_roll.hip, epilogue_sw).
+    // takes out-of-range offsets: nothing is stored), through cr_transpose:
+    // the lane then holds chunk ecc of voxels (r & 15) + 16 q in v[8 q .. + 7].
     auto flush = [&](const f32x16& A, int orow) __attribute__((always_inline)) {
       const bool rv = orow >= r0 && orow < r1;
       float v[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) v[i] = A[i];
-#pragma unroll
-      for (int g = 0; g < 4; g += 2) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const auto sw = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, v[4 * g + i]),
-                                                           __builtin_bit_cast(uint32_t, v[4 * g + 4 + i]), false, false);
-          v[4 * g + i] = __builtin_bit_cast(float, (uint32_t)sw[0]);
-          v[4 * g + 4 + i] = __builtin_bit_cast(float, (uint32_t)sw[1]);
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const auto sw = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(uint32_t, v[e]),
-                                                         __builtin_bit_cast(uint32_t, v[8 + e]), false, false);
-        v[e] = __builtin_bit_cast(float, (uint32_t)sw[0]);
-        v[8 + e] = __builtin_bit_cast(float, (uint32_t)sw[1]);
-      }
+      cr_transpose(A, v);
       float bsv[8];
       {
         const float4 c0 = *reinterpret_cast<const float4*>(lbias + ech);
@@ -397,43 +335,25 @@ int vsrk_conv_fwd_row(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void
   if (em != 0 && em != CE_RELU && em != CE_RES && em != CE_MASK && em != (CE_RES | CE_ACC)) return 0;
   if (mode < 0 && !cr_default_on(em)) return 0;
   if (!chunk_ok(x, 2)) return 0;
-  for (const vsrk_tensor5* t : {x, y, residual, mask}) {
-    if (!t) continue;
-    // every byte offset inside one image fits the buffer range (exact reads: no over-read margin)
-    const int64_t span = (int64_t)(t->h - 1) * t->sh + (int64_t)(t->w - 1) * t->sw + 64;
-    if (t->sn < 0 || t->sd < 0 || t->sh < 0 || t->sw < 0 || 2 * span >= 0x7FFFFFF0ll) return 0;
-    if (t->sh >= (1ll << 30) || t->sw >= (1ll << 30)) return 0;
-  }
+  for (const vsrk_tensor5* t : {x, y, residual, mask})
+    if (t && !cr_view_fits(t, t->h, t->w)) return 0;
   const int64_t nimg = (int64_t)y->n * y->d;
   if (nimg == 0 || y->h == 0 || y->w == 0) return 1;
-  auto view = [](const vsrk_tensor5* t) {
-    CrView v;
-    v.ptr = (const char*)t->ptr;
-    v.sn = t->sn; v.sd = t->sd; v.sh = (int)t->sh; v.sw = (int)t->sw;
-    return v;
-  };
+  CrPlan p;
+  if (!cr_plan(nimg, y->h, y->w, p)) return 0;
   ConvRowArgs a;
-  a.x = view(x);
-  a.y = view(y);
-  a.res = view(residual ? residual : y);
-  a.msk = view(mask ? mask : y);
+  a.x = cr_view(x);
+  a.y = cr_view(y);
+  a.res = cr_view(residual ? residual : y);
+  a.msk = cr_view(mask ? mask : y);
   a.w = w_packed;
   a.bias = bias;
   a.cin_pad = round_up(x->c, 32);
   a.cout_pad = round_up(y->c, 128);
   a.out_scale = d->out_scale;
   a.D = y->d; a.H = y->h; a.W = y->w;
-  a.nseg = ceil_div(y->w, CR_SEG);
-  // bands: as many as it takes for the (capped) grid to cover the CUs
-  const int64_t target = vsrk_capped_grid(vsrk_num_cus());
-  const int64_t cols = nimg * a.nseg;
-  int64_t nb = std::max<int64_t>(1, std::min<int64_t>(ceil_div64(target, cols), y->h));
-  a.band_h = (int)std::max<int64_t>(ceil_div64(y->h, nb), std::min(CR_MINBAND, y->h));
-  a.nband = ceil_div(y->h, a.band_h);
-  const int64_t nitems = cols * a.nband;
-  if (nitems >= (1ll << 31)) return 0;
-  a.nitems = (int)nitems;
-  const int grid = (int)vsrk_capped_grid(std::min<int64_t>(nitems, vsrk_num_cus()));
+  a.nseg = p.nseg; a.nband = p.nband; a.band_h = p.band_h; a.nitems = p.nitems;
+  const int grid = p.grid;
   int rc = vsrk_dispatch16(x->dtype, [&](auto tag) {
     using H = decltype(tag);
     switch (em) {

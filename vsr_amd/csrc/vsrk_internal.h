@@ -75,6 +75,17 @@ int vsrk_conv_fwd_roll_fold(const vsrk_conv_desc* d, const vsrk_tensor5* x, cons
 int vsrk_conv_fwd_row(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed, const float* bias,
                       const vsrk_tensor5* residual, const vsrk_tensor5* mask, const vsrk_tensor5* y, hipStream_t s);
 
+// row-walking 16-bit Conv 3x3 64 -> 256 through a shuffle-2 output view
+// (conv_row_wide.hip): forward of EDSR's up-sampler convs, reached from
+// conv_roll.hip's sub-pixel output branch after its checks; same return
+// convention.  vsrk_g_row_wide_mode (vsrk_conv_set_row_wide, conv_paths.hip): -1
+// default (VSRK_CONV_ROW_WIDE unset: the shapes that measured faster than the
+// tile kernel), 0 off, 1 every shape
+extern int vsrk_g_row_wide_mode;
+int vsrk_conv_fwd_row_wide(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed, const float* bias,
+                           const vsrk_tensor5* residual, const vsrk_tensor5* mask, const vsrk_tensor5* y,
+                           hipStream_t s);
+
 // pointwise (1x1x1) bf16 conv (conv_pw.hip): forward / data gradient; same
 // return convention (its weight gradient: conv_wgrad.h)
 int vsrk_conv_fwd_pw(const vsrk_conv_desc* d, const vsrk_tensor5* x, const void* w_packed, const float* bias,

@@ -411,8 +411,8 @@ def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, k, pad, dw: torch.Tensor, dbia
 
 
 def set_conv_path(path: str, mode: int) -> None:
-    """Select a conv kernel family ("fast", "pw", "pw_wide", "roll", "roll_wr", "roll_fold", "row", "thin",
-    "stencil", "wgrad_pipe", "wgrad_roll", "wgrad_row"): 0 off, 1 on, -1 back
+    """Select a conv kernel family ("fast", "pw", "pw_wide", "roll", "roll_wr", "roll_fold", "row", "row_wide",
+    "thin", "stencil", "wgrad_pipe", "wgrad_roll", "wgrad_row"): 0 off, 1 on, -1 back
     to the mode resolved from the family's environment variable when the
     library was loaded (the table is in include/vsrk.h)
     (for "roll" / "wgrad_roll": 1 forces the rolling kernel on every eligible
@@ -422,14 +422,25 @@ def set_conv_path(path: str, mode: int) -> None:
     epilogue, where they are slower, and 0 or 2 keep the row kernel aside;
     "row": the row-walking 3x3 64 -> 64 conv of EDSR's body, reached through
     "roll"; its default routes the epilogue forms that measured faster than
-    the tile kernel, 1 routes every form it covers).  A process-wide test /
+    the tile kernel, 1 routes every form it covers; "row_wide": the
+    row-walking 3x3 64 -> 256 conv through a shuffle-2 output view, EDSR's
+    up-sampler forward, also reached through "roll"; its default routes the
+    shapes that measured faster than the tile kernel, 1 every eligible
+    shape; the library keeps it as a knob of its own, vsrk_conv_set_row_wide,
+    beside its table of paths).  A process-wide test /
     A-B switch: set it between launches, not concurrently with them."""
+    if path == "row_wide":
+        N.check(_lib().vsrk_conv_set_row_wide(int(mode)), "conv_set_row_wide")
+        return
     N.check(_lib().vsrk_conv_set_path(path.encode(), int(mode)), "conv_set_path")
 
 
 def get_conv_path(path: str) -> int:
     """The effective mode of a conv kernel family (see set_conv_path)."""
     mode = C.c_int32()
+    if path == "row_wide":
+        N.check(_lib().vsrk_conv_get_row_wide(C.byref(mode)), "conv_get_row_wide")
+        return mode.value
     N.check(_lib().vsrk_conv_get_path(path.encode(), C.byref(mode)), "conv_get_path")
     return mode.value
 
